@@ -17,6 +17,11 @@ The SNIP mask phase runs once before the warmup rounds (as in the reference, it 
 ``--aggregator``], dispfl, subavg, ditto, dpsgd, fedfomo, local) and ``--size-skew A`` gives the clients
 Dirichlet(A) sizes with the same total sample count (ragged federations).
 
+A plain run does only what the headline figure needs: setup, the SNIP mask, the warmup rounds, the ``--steps`` timed
+rounds and the result line (``ms_per_step`` = wall milliseconds of one timed round).  ``--dump-outputs DIR`` also
+writes what the last timed round left (``dump_outputs``); the inputs depend on the arguments alone, so two builds
+can be compared output for output.  Measurements beyond the headline go behind ``--full`` (none exist today).
+
 Data: synthetic ABCD-shape (1x121x145x121 uint8) volumes with a non-IID (Dirichlet 0.3) label prior per
 client, generated on device; random-init AlexNet3D_Dropout weights.  Compute: bf16 MFMA with fp32 accumulate,
 fp32 master weights / optimizer / BN statistics.
@@ -67,6 +72,13 @@ def parse(argv=None):
     ap.add_argument("--dump-rows", default="", help="after the run, save this rank's client rows (each client's "
                     "last locally trained params, i.e. the rows before the last aggregation) to <prefix>.rank<r>.pt "
                     "(sharding-parity checks: tools/compare_rows.py)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed round left (global model, client rows, "
+                         "round metrics) to DIR/<name>.npy; see dump_outputs()")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none at present: a plain run already "
+                         "does only setup, warmup, the timed steps and the result line; extra measurements added "
+                         "later belong behind this flag)")
     ap.add_argument("--step-streams", type=int, default=4,
                     help="side streams for the extra (ragged) launches of one lockstep step (1 = serial)")
     ap.add_argument("--rebalance", type=int, default=0,
@@ -169,6 +181,57 @@ def _cpu_tiny_setup(args, info):
     torch.manual_seed(args.seed)
     model = Tiny3D()
     return model, TorchEngine(model, vols, labels, "cpu"), splits, [args.train_per_client] * args.clients
+
+
+DUMP_ROW_BYTES = 32 << 20   # --dump-outputs: budget of each client-row matrix (the whole dump stays under 64 MB)
+DUMP_VEC_BYTES = 8 << 20    # ... and of each single vector
+
+
+def _dump_cols(n, rows, budget, seed):
+    """Column indices (sorted) of an [rows, n] fp32 matrix that fit ``budget`` bytes: all of them, or a fixed
+    sample drawn from ``seed`` alone, so two builds run with the same arguments keep the same columns."""
+    import numpy as np
+    k = max(1, budget // (4 * max(1, rows)))
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.RandomState(seed).permutation(n)[:k]).astype(np.int64)
+
+
+def dump_outputs(dirname, runner, res, args, info):
+    """``--dump-outputs DIR``: what the last timed round left for its caller, as float32 / float64 ``.npy`` files.
+
+    * ``w_global`` / ``b_global``: the aggregated parameters / BN buffers (flat, the engine's layout order);
+    * ``client_params`` / ``client_bufs``: this rank's client rows (each client's last locally trained state), one
+      row per client in client-id order;
+    * ``last_round_metrics``: the round's metric values in the order of their sorted names (float64).
+
+    A matrix or vector over its byte budget is cut to a fixed column sample (``_dump_cols``, seeded by ``--seed``).
+    Rank 0 writes the global arrays and the metrics; with more than one rank the client-row files carry a
+    ``.rank<r>`` infix (each rank holds its own shard)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    dev = runner.device
+
+    def save(name, t):
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(t.detach().float().cpu().numpy()))
+
+    def cols_of(n, rows, budget, salt):
+        return torch.as_tensor(_dump_cols(n, rows, budget, args.seed + salt), device=dev)
+
+    if info.is_main:
+        save("w_global", runner.w_global[:runner.P][cols_of(runner.P, 1, DUMP_VEC_BYTES, 1)])
+        save("b_global", runner.b_global[:runner.Q][cols_of(runner.Q, 1, DUMP_VEC_BYTES, 2)])
+        vals = [] if res is None else [float(v) for _, v in sorted(dict(res).items()) if np.isscalar(v)]
+        np.save(os.path.join(dirname, "last_round_metrics.npy"), np.asarray(vals, dtype=np.float64))
+    rows, loc = runner._local_rows(range(args.clients))
+    if rows:
+        order = np.argsort(np.asarray(loc))
+        ix = torch.as_tensor(np.asarray(rows)[order], device=dev)
+        tag = "" if info.world == 1 else ".rank%d" % info.rank
+        pc = cols_of(runner.P, args.clients, DUMP_ROW_BYTES, 3)  # budget over all ranks: the same columns on each
+        bc = cols_of(runner.Q, args.clients, DUMP_VEC_BYTES, 4)
+        save("client_params" + tag, runner.theta[ix[:, None], pc[None, :]])
+        save("client_bufs" + tag, runner.bufs[ix[:, None], bc[None, :]])
 
 
 def main(argv=None):
@@ -277,6 +340,8 @@ def run(args):
                                 info)
     ms = dt * 1000.0 / max(1, args.steps)
     value = args.steps / dt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, runner, res, args, info)
     headline = (cuda and args.algorithm == "salientgrads" and args.clients == 64 and args.aggregator == "fedavg"
                 and args.size_skew == 0 and args.frac == 1.0)
     if info.is_main:

@@ -80,6 +80,39 @@ def test_torchrun_launch_shape_still_works():
     assert _json(r, strict=False)["n_gpus"] == 2
 
 
+def test_dump_outputs_repeatable_and_full_flag_accepted(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed round's arrays as float ``.npy`` files, identical from run to run
+    with the same arguments; ``--full`` is accepted and leaves the result line's keys as they are."""
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = _json(_run([sys.executable, BENCH, "--gpus", "1", "--dump-outputs", str(d)] + TINY + extra))
+        assert out["steps"] == 1 and out["ms_per_step"] > 0
+        runs.append((out, {f: np.load(d / f) for f in sorted(os.listdir(d))}))
+    (one, a), (two, b) = runs
+    assert set(one) == set(two)
+    assert set(a) == {"w_global.npy", "b_global.npy", "client_params.npy", "client_bufs.npy",
+                      "last_round_metrics.npy"} == set(b)
+    assert a["client_params.npy"].shape == (8, a["w_global.npy"].size)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    vals = [v for _, v in sorted(one["last_round_metrics"].items())]
+    assert np.array_equal(a["last_round_metrics.npy"], np.asarray(vals))
+    for f, v in a.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), f
+        assert np.array_equal(v, b[f]), f
+
+
+def test_dump_cols_sample_is_fixed_and_within_budget():
+    sys.path.insert(0, ROOT)
+    import bench
+    full = bench._dump_cols(1000, 4, 1 << 20, seed=3)
+    assert np.array_equal(full, np.arange(1000))
+    cols = bench._dump_cols(100000, 64, 64 * 4 * 500, seed=3)
+    assert cols.size == 500 and np.all(np.diff(cols) > 0) and cols[-1] < 100000
+    assert np.array_equal(cols, bench._dump_cols(100000, 64, 64 * 4 * 500, seed=3))
+    assert not np.array_equal(cols, bench._dump_cols(100000, 64, 64 * 4 * 500, seed=4))
+
+
 def test_rank_count_mismatch_fails_loudly():
     env = _env()
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_port()))
