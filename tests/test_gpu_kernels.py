@@ -3,6 +3,10 @@
 All tests run in one process on the GPU box (``pytest -m gpu``).  Shapes are the real AlexNet3D shapes at the
 ABCD input (1x121x145x121) with small client/batch counts, and every launch's operands are validated on the
 host by the Python wrappers first.
+
+The conv comparisons here are whole-tensor relative norms on random data (bf16 storage noise sets their thresholds);
+tests/test_gpu_exact_conv.py holds the same kernels to bit equality on integer operands, where a single wrong tap or
+position fails.
 """
 import numpy as np
 import pytest
