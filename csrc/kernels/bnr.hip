@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256) void k_bnr_bwd_apply(const uint16_t* __restric
 
 static void bnr_check(int G, int64_t M, int C, const char* who) {
   NIDT_REQUIRE(G > 0 && M > 0 && C % 8 == 0 && C <= 2048 && kBnrThreads % (C / 8) == 0,
-               std::string(who) + ": C a power-of-two multiple of 8, <= 2048");
+               std::string(who) + ": C must be a multiple of 8, <= 2048, with C/8 dividing 256");
   NIDT_REQUIRE(M < (1ll << 31), std::string(who) + ": positions per client < 2^31");
 }
 
