@@ -17,6 +17,14 @@ void rows_nnz(uintptr_t rows, int64_t R, int64_t P, int64_t stride, uintptr_t pa
 void weighted_rows_sum(uintptr_t rows, uintptr_t wts, int64_t C, int64_t P, int64_t stride, float beta, uintptr_t out,
                        uintptr_t stream);
 void broadcast_row(uintptr_t src, int64_t P, int64_t stride, int64_t C, uintptr_t dst, uintptr_t stream);
+// defense.hip
+int64_t rows_diff_norm_blocks(int64_t P);
+void rows_diff_norm(uintptr_t rows, uintptr_t ref, int64_t C, int64_t P, int64_t stride, uintptr_t part,
+                    uintptr_t norm, uintptr_t stream);
+void clipped_rows_sum(uintptr_t rows, uintptr_t ref, uintptr_t wts, uintptr_t norm, uintptr_t cids, int64_t C,
+                      int64_t P, int64_t stride, float norm_bound, float stddev, uint64_t seed, uintptr_t mbits,
+                      uintptr_t out, uintptr_t stream);
+// optim.hip
 void local_opt(uintptr_t w, uintptr_t g, uintptr_t buf, int64_t ld, uintptr_t mbits, int64_t mstride, int mask_mode,
                uintptr_t ref, int64_t ref_ld, float mu, uintptr_t pref, int64_t pref_ld, float lamda, uintptr_t part,
                int64_t C, int64_t P, float lr, float wd, float mom, float max_norm, uintptr_t lr_dev, int keep_grad,
@@ -272,6 +280,9 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(clip_sgd_mask_workspace);
   DEF(clip_sgd_mask);
   DEF(weighted_rows_sum);
+  DEF(rows_diff_norm_blocks);
+  DEF(rows_diff_norm);
+  DEF(clipped_rows_sum);
   DEF(rows_nnz_blocks);
   DEF(rows_nnz);
   DEF(broadcast_row);

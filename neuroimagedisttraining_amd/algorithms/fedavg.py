@@ -21,8 +21,23 @@ from ..core import robustness as R
 
 class FedAvgAPI(APIBase):
 
-    def _aggregate(self, w_locals):
+    def _aggregate(self, w_locals, w_global=None):
+        """Sample-weighted mean (or ``args.aggregator``).  With ``args.defense_type`` in {``norm_diff_clipping``,
+        ``weak_dp``} and the current global state ``w_global``, every client first goes through the reference's
+        ``RobustAggregator`` (``robust_aggregation.py:32-55``): its update over the weight parameters is clipped to
+        ``args.norm_bound``; ``weak_dp`` then adds ``torch.randn * args.stddev`` to those entries.  This is the
+        reference-semantics oracle for the executor's clipping (``engine/defense.py``), not for its noise bits."""
         kind = getattr(self.args, "aggregator", "fedavg") or "fedavg"
+        defense = getattr(self.args, "defense_type", None) or "none"
+        if defense != "none" and kind == "fedavg" and w_global is not None:
+            ra = R.RobustAggregator(self.args)
+            clipped = []
+            for n, w in w_locals:
+                w = ra.norm_diff_clipping(w, w_global)
+                if defense == "weak_dp":
+                    w = {k: ra.add_noise(v) if R.is_weight_param(k) else v for k, v in w.items()}
+                clipped.append((n, w))
+            w_locals = clipped
         if kind == "fedavg":
             return super()._aggregate(w_locals)
         return R.robust_aggregate(kind, w_locals, f=int(getattr(self.args, "byzantine_f", 0) or 0),
@@ -49,7 +64,7 @@ class FedAvgAPI(APIBase):
                 w_locals.append((client.get_sample_number(), w))
                 self.stat_info["sum_training_flops"] += flops
                 self.stat_info["sum_comm_params"] += comm
-            w_global = self._aggregate(w_locals)
+            w_global = self._aggregate(w_locals, w_global)
             freq = max(1, int(getattr(self.args, "frequency_of_the_test", 1) or 1))
             if round_idx % freq == 0 or round_idx == self.args.comm_round - 1:
                 self._test_on_all_clients(w_global, w_per_mdls, round_idx)

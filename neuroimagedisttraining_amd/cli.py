@@ -14,6 +14,13 @@ the reference entry points.  Added flags:
   ``--synthetic_size N``: N synthetic train images (N/5 test) for CIFAR/Tiny without data files.
 * FedProx / robust aggregation: ``--fedprox_mu``, ``--aggregator {fedavg,krum,multikrum,median,trimmed_mean}``,
   ``--byzantine_f``, ``--trim_ratio``.
+* ``--defense_type {none,norm_diff_clipping,weak_dp}``, ``--norm_bound``, ``--stddev`` (the names the reference's
+  ``RobustAggregator`` reads): every client's update ``w_i - w_g`` over the weight parameters is clipped to an L2
+  ball of radius ``norm_bound`` before the FedAvg mean; ``weak_dp`` then adds ``N(0, stddev^2)`` per client.  On the
+  HIP executor two streaming kernels over the client rows (``engine/defense.py``; counter-based noise, and under a
+  SalientGrads mask only on the kept coordinates); on the eager path ``RobustAggregator`` itself with
+  ``torch.randn``.  FedAvg-style aggregation only: not with ``--aggregator`` other than ``fedavg``, ``--update_topk``
+  or the personalized algorithms (``ValueError``).
 * ``--checkpoint_dir`` / ``--checkpoint_every`` / ``--keep_last`` / ``--resume`` for the HIP executor (background-written,
   indexed, world-size independent checkpoints: ``utils/checkpoint.py``).
 
@@ -29,6 +36,9 @@ import random
 import numpy as np
 import torch
 
+DEFENSES = ("none", "norm_diff_clipping", "weak_dp")
+# algorithms whose runner forms FedAvg's global weighted mean (the only aggregation --defense_type applies to)
+DEFENDED_ALGOS = ("sailentgrads", "salientgrads", "fedavg", "fedprox")
 ALGOS = ("sailentgrads", "fedavg", "fedprox", "dispfl", "subavg", "ditto", "dpsgd", "fedfomo", "local")
 
 _DEFAULTS = {  # per-entry-point defaults that differ
@@ -123,6 +133,10 @@ def add_args(parser, algo):
     a("--byzantine_f", type=int, default=0)
     a("--trim_ratio", type=float, default=0.1)
     a("--update_topk", type=float, default=0.0, help="send only the top-k fraction of each client's update")
+    a("--defense_type", type=str, default="none", choices=list(DEFENSES),
+      help="norm_diff_clipping: clip each client's update to --norm_bound; weak_dp: clip, then N(0, --stddev^2) noise")
+    a("--norm_bound", type=float, default=5.0)
+    a("--stddev", type=float, default=0.025)
     a("--group", type=int, default=0)
     a("--checkpoint_dir", type=str, default="")
     a("--checkpoint_every", type=int, default=1,
@@ -365,6 +379,10 @@ def fl_config(args, algo):
     """FLConfig from the reference flags of any entry point."""
     from .engine.executor import FLConfig
     g = lambda k, d=None: getattr(args, k, d)  # noqa: E731
+    defense = g("defense_type", "none") or "none"
+    if defense != "none" and algo not in DEFENDED_ALGOS:
+        raise ValueError("defense_type=%s cannot be combined with algorithm=%s (only sailentgrads / fedavg / fedprox)"
+                         % (defense, algo))
     return FLConfig(comm_round=args.comm_round, epochs=args.epochs, batch_size=args.batch_size, lr=args.lr,
                     lr_decay=args.lr_decay, wd=args.wd, momentum=args.momentum, frac=args.frac,
                     dense_ratio=g("dense_ratio", 1.0), itersnip_iteration=g("itersnip_iteration", 1),
@@ -381,7 +399,8 @@ def fl_config(args, algo):
                     different_initial=bool(g("different_initial", False)), diff_spa=bool(g("diff_spa", False)),
                     erk_power_scale=g("erk_power_scale", 1.0), save_masks=bool(g("save_masks", False)),
                     dispfl_aggregate=bool(g("dispfl_aggregate", 0)), each_prune_ratio=g("each_prune_ratio", 0.05),
-                    dist_thresh=g("dist_thresh", 1e-4), acc_thresh=g("acc_thresh", 0.5))
+                    dist_thresh=g("dist_thresh", 1e-4), acc_thresh=g("acc_thresh", 0.5),
+                    defense_type=defense, norm_bound=g("norm_bound", 5.0), stddev=g("stddev", 0.025))
 
 
 def image_cohort(args, info, with_val=False):
@@ -548,6 +567,8 @@ def main(algo, argv=None):
     args = parser.parse_args(argv)
     args.algo = algo
     args.identity = identity(args, algo)
+    if args.defense_type != "none":
+        fl_config(args, algo)  # rejected combinations fail here on either engine, before any data is loaded
     log_path = os.path.join(args.log_dir, args.dataset, args.identity + ".log")
     logger = logger_config(log_path=log_path, logging_name=args.identity)
     logger.info(args)

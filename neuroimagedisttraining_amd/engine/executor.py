@@ -103,6 +103,26 @@ class FLConfig:
                                   # number of samples; the data stays sharded like the clients
     heartbeat_s: float = 0.0      # >0: ranks publish heartbeats every heartbeat_s through the process group's store and
                                   # each round fails fast (comm.failure.PeerFailure) if a peer is silent for 30x that
+    # ---- the reference's RobustAggregator on the FedAvg row sum (engine/defense.py, csrc/kernels/defense.hip)
+    defense_type: str = "none"    # none | norm_diff_clipping | weak_dp (clipping, then N(0, stddev^2) per client)
+    norm_bound: float = 5.0       # L2 radius each client's update w_i - w_g (weight params only) is clipped to
+    stddev: float = 0.025         # weak_dp noise scale
+
+    def __post_init__(self):
+        if self.defense_type not in ("none", "norm_diff_clipping", "weak_dp"):
+            raise ValueError("defense_type %r: one of none | norm_diff_clipping | weak_dp" % (self.defense_type,))
+        if self.defense_type != "none":
+            # the defence rides on FedAvg's weighted row sum; it is not defined for the gathered robust aggregators
+            # or the sparse top-k update exchange
+            if self.aggregator != "fedavg":
+                raise ValueError("defense_type=%s cannot be combined with aggregator=%s (only aggregator=fedavg)"
+                                 % (self.defense_type, self.aggregator))
+            if self.update_topk > 0:
+                raise ValueError("defense_type=%s cannot be combined with update_topk=%s (only update_topk=0)"
+                                 % (self.defense_type, self.update_topk))
+            if not self.norm_bound > 0 or self.stddev < 0:
+                raise ValueError("defense_type=%s needs norm_bound > 0 and stddev >= 0 (got %s, %s)"
+                                 % (self.defense_type, self.norm_bound, self.stddev))
 
 
 # ------------------------------------------------------------------------------------------------

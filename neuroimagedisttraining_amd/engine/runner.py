@@ -88,7 +88,8 @@ class StatInfo(dict):
     still in flight (:meth:`FLRunner._flush_metrics`), so every consumer sees the complete, ordered lists while a timed
     GPU loop never waits for a metric."""
 
-    DEFERRED = ("global_test_acc", "global_test_loss", "person_test_acc", "person_test_loss", "test_acc")
+    DEFERRED = ("global_test_acc", "global_test_loss", "person_test_acc", "person_test_loss", "test_acc",
+                "defense_clipped", "defense_max_ratio")
 
     def __init__(self, flush, *a, **kw):
         super().__init__(*a, **kw)
@@ -916,6 +917,8 @@ class FLRunner:
         self.add_comm(down + self.state_nonzeros(self.theta, self.bufs, rows), loc)  # + uplink (the local model)
 
     def aggregate(self, sampled):
+        if self.cfg.defense_type != "none":
+            return self.aggregate_defended(sampled)
         if self.cfg.aggregator != "fedavg":
             return self.aggregate_robust(sampled)
         if self.cfg.update_topk > 0:
@@ -1020,7 +1023,12 @@ class FLRunner:
         n_tot = float(sum(self.sizes[c] for c in sampled))
         rows, loc = self._local_rows(sampled)
         buf, Pp = self.weighted_partial(self.theta, self.bufs, rows, [self.sizes[c] / n_tot for c in loc])
-        sparse = (self.info.enabled and self.cfg.sparse_aggregate and self.alg == "salientgrads"
+        self._reduce_partial(buf, Pp)
+
+    def _reduce_partial(self, buf, Pp, compact=True):
+        """All-reduce a ``[Pp + Q]`` partial (only the mask-compacted coordinates when a SalientGrads mask is
+        active and ``compact``) and install it as the global model."""
+        sparse = (compact and self.info.enabled and self.cfg.sparse_aggregate and self.alg == "salientgrads"
                   and self.mask is not None)
         if sparse:
             idx = self._compact_index(Pp)
@@ -1034,6 +1042,71 @@ class FLRunner:
             self.stat_info["aggregate_elems"] = int(buf.numel())
         self.w_global.copy_(buf[:self.P])
         self.b_global.copy_(buf[Pp:])
+
+    def aggregate_defended(self, sampled):
+        """FedAvg with the reference's ``RobustAggregator`` applied to every client first
+        (``robust_aggregation.py:32-55``): each update ``theta_i - w_global`` is clipped to the L2 ball of radius
+        ``cfg.norm_bound``; ``weak_dp`` then adds ``N(0, cfg.stddev^2)`` to the client's weights.  Two streaming
+        passes over this rank's rows in place (``engine/defense.py``: norms, then the clipped weighted sum), BN
+        buffers summed as in FedAvg, the same single all-reduce.
+
+        The reference clips and perturbs the entries ``is_weight_param`` keeps (everything but ``running_mean`` /
+        ``running_var`` / ``num_batches_tracked``) and averages the rest untouched.  That is exactly the ``theta`` /
+        ``bufs`` split of ``ParamLayout``: ``theta`` holds ``named_parameters()``, ``bufs`` holds
+        ``named_buffers()``, and the only buffers of the engines' models (AlexNet3D, 3D ResNet-50: BatchNorm; the
+        ResNet-18-GN has none) are those three BatchNorm entries (``tests/test_cpu_defense.py`` checks it).
+
+        The noise is a counter-based function of (cfg.seed, round, global client id, coordinate), so the result does
+        not depend on the sharding.  Deviation from the reference: under a SalientGrads mask the noise is confined to
+        the kept coordinates, so a pruned weight that is 0 on every client and in ``w_global`` stays exactly 0.
+
+        The all-reduce is dense even under a SalientGrads mask.  The compacted exchange of :meth:`aggregate_fedavg`
+        relies on the weighted sum being 0 at pruned coordinates; here it is not: the initial global model is dense
+        while the clients' pruned weights are 0, so a clipped client contributes ``w_global * (1 - 1 / m_c)`` there
+        (``RobustAggregator`` gives the same), and that residue only shrinks geometrically over the rounds.
+
+        ``stat_info["defense_clipped"]`` / ``["defense_max_ratio"]``: the round's number of clipped clients and
+        largest ``norm / norm_bound`` (kept on the device here, read where the deferred metrics are)."""
+        from . import defense as DF
+        cfg = self.cfg
+        stddev = float(cfg.stddev) if cfg.defense_type == "weak_dp" else 0.0
+        n_tot = float(sum(self.sizes[c] for c in sampled))
+        rows, loc = self._local_rows(sampled)
+        Pp = (self.P + 63) // 64 * 64
+        buf = torch.zeros(Pp + self.Q, dtype=torch.float32, device=self.device)
+        # [clipped count | largest ratio of rank 0, 1, ...]: one SUM all-reduce carries both
+        st = torch.zeros(1 + self.info.world, dtype=torch.float32, device=self.device)
+        if rows:
+            w = self._to_dev([self.sizes[c] / n_tot for c in loc], torch.float32)
+            fast = self.device.type == "cuda" and _contiguous(rows)
+            if fast:
+                th, bu = self.theta[rows[0]:rows[-1] + 1], self.bufs[rows[0]:rows[-1] + 1]
+            else:
+                ix = self._to_dev(rows)
+                th, bu = self.theta.index_select(0, ix), self.bufs.index_select(0, ix)
+            bits = self.mask_bits if (self.alg == "salientgrads" and stddev > 0) else None
+            norm = DF.rows_diff_norm(th, self.w_global, hip=fast)
+            DF.clipped_rows_sum(th, self.w_global, w, norm, self._to_dev(loc, torch.int32) if fast else loc,
+                                cfg.norm_bound, stddev, DF.round_seed(cfg.seed, getattr(self, "_round_idx", 0)), buf,
+                                mbits=bits, hip=fast)
+            if self.Q:  # BN buffers: plain weighted sum (no clipping, no noise)
+                if fast:
+                    ops.ext().weighted_rows_sum(bu.data_ptr(), w.data_ptr(), len(rows), self.Q, bu.stride(0), 0.0,
+                                                buf[Pp:].data_ptr(), ops.stream())
+                else:
+                    buf[Pp:] = (w.view(-1, 1) * bu[:, :self.Q]).sum(0)
+            ratio = norm / torch.full((1,), float(cfg.norm_bound), dtype=torch.float32, device=self.device)
+            st[0] = (ratio > 1).sum()
+            st[1 + self.info.rank] = ratio.max()
+        self._reduce_partial(buf, Pp, compact=False)
+        rt.all_reduce_buckets(st, self.info)
+        self._defer_result(getattr(self, "_round_idx", 0), torch.stack([st[0], st[1:].max()]).double(),
+                           recorder=self._record_defense)
+
+    def _record_defense(self, round_idx, r):
+        dict.__setitem__(self.stat_info, "defense_clipped", int(round(float(r[0]))))
+        dict.__setitem__(self.stat_info, "defense_max_ratio", float(r[1]))
+        return dict(defense_clipped=int(round(float(r[0]))), defense_max_ratio=float(r[1]))
 
     def aggregate_robust(self, sampled):
         """Byzantine-robust aggregation (BASELINE config 4): every sampled client's (params, buffers) row is
@@ -1402,6 +1475,7 @@ class FLRunner:
         return self._hb or None
 
     def _round_start(self, round_idx):
+        self._round_idx = round_idx  # keys the round's weak-DP noise (aggregate_defended)
         hb = self._heartbeat()
         if hb is not None:
             hb.check_or_raise()  # before the round's collectives: a dead peer would block them until the timeout
