@@ -5,6 +5,7 @@
 #include <hip/hip_bf16.h>
 #include <algorithm>
 #include <cstdint>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -88,6 +89,18 @@ template <typename T>
 inline T* ptr(uintptr_t p) { return reinterpret_cast<T*>(p); }
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// Integer switch from the environment (NIDT_*), dflt when unset.  Call sites keep the value in a function-local
+// `static const`, so a switch is read once per process, at its first use.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+inline int64_t env_int64(const char* name, int64_t dflt) {
+  const char* e = getenv(name);
+  return e ? (int64_t)atoll(e) : dflt;
+}
 
 // Bijective XCD-aware remap of a 1-D block id (cdna_hip_programming.md §5, "XCD swizzle must be bijective"):
 // consecutive logical tiles land on the same XCD so neighbouring tiles share that XCD's L2.

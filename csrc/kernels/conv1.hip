@@ -248,19 +248,13 @@ __global__ void k_pack_conv1_w(const float* __restrict__ theta, int64_t ldt, int
 int conv1_kslots();
 int conv1_fwd_variant();
 int conv1_tapord() {
-  static const int env = [] {
-    const char* e = getenv("NIDT_C1_TAPORD");
-    return e ? atoi(e) : 0;
-  }();
+  static const int env = env_int("NIDT_C1_TAPORD", 0);
   if (conv1_fwd_variant() == 1 && conv1_kslots() == 128) return env >= 0 && env <= 2 ? env : 0;
   return env == 1 ? 1 : 0;
 }
 
 int conv1_kslots() {
-  static const int ks = [] {
-    const char* e = getenv("NIDT_C1_K224");
-    return (e && atoi(e) == 1) ? kK1 : 128;
-  }();
+  static const int ks = env_int("NIDT_C1_K224", 0) == 1 ? kK1 : 128;
   return ks;
 }
 
@@ -903,10 +897,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_fwd_w64(const uint8_t* __restr
 static int g_c1fwd_mode = -1;
 void conv1_fwd_mode(int mode) { g_c1fwd_mode = mode; }
 int conv1_fwd_variant() {
-  static const int v = [] {
-    const char* e = getenv("NIDT_C1_FWD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = env_int("NIDT_C1_FWD", 1);
   return g_c1fwd_mode >= 0 ? g_c1fwd_mode : v;
 }
 
@@ -914,16 +905,10 @@ void conv1_fwd_pool(uintptr_t x8, uintptr_t idx, uintptr_t w8, uintptr_t scale, 
                     uintptr_t out, uintptr_t amax, uintptr_t stream) {
   NIDT_REQUIRE(NB % B == 0, "conv1_fwd_pool: NB % B");
   if (conv1_fwd_variant() == 1 && conv1_kslots() == 128) {
-    static const int nq1 = [] {
-      const char* e = getenv("NIDT_C1_NQ");
-      return e ? std::max(1, std::min(kPH, atoi(e))) : 1;
-    }();
+    static const int nq1 = std::max(1, std::min(kPH, env_int("NIDT_C1_NQ", 1)));
     // B-fragment prefetch distance of the RO = 2 kernel in k-steps (NIDT_C1_WPF, A/B), default 4 (3.28 ms per
     // 64-client step vs 3.35 at 2; the RO = 0 kernel, 45.7 % bank conflicts, also 3.28: profiles/r6_conv1_b128.txt)
-    static const int wpf = [] {
-      const char* e = getenv("NIDT_C1_WPF");
-      return e ? atoi(e) : 4;
-    }();
+    static const int wpf = env_int("NIDT_C1_WPF", 4);
     if (conv1_tapord() == 2 && wpf == 3)
       hipLaunchKernelGGL((k_conv1_fwd_w64<3, 2>), dim3(kPD * NB * nq1), dim3(256), 0, as_stream(stream),
                          ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
@@ -948,19 +933,10 @@ void conv1_fwd_pool(uintptr_t x8, uintptr_t idx, uintptr_t w8, uintptr_t scale, 
     return;
   }
   // B-fragment prefetch distance (k-steps); NIDT_C1_PF=1/2/3 selects it (A/B), default 2
-  static const int pf = [] {
-    const char* e = getenv("NIDT_C1_PF");
-    return e ? atoi(e) : 2;
-  }();
-  static const int occ = [] {
-    const char* e = getenv("NIDT_C1_OCC");
-    return e ? atoi(e) : 2;
-  }();
+  static const int pf = env_int("NIDT_C1_PF", 2);
+  static const int occ = env_int("NIDT_C1_OCC", 2);
   // pooled-row split per slab: NIDT_C1_NQ (A/B), default 1
-  static const int nq_env = [] {
-    const char* e = getenv("NIDT_C1_NQ");
-    return e ? std::max(1, std::min(kPH, atoi(e))) : 1;
-  }();
+  static const int nq_env = std::max(1, std::min(kPH, env_int("NIDT_C1_NQ", 1)));
   const int nq = nq_env;
 #define NIDT_C1(PF, KSS)                                                                                       \
   if (occ == 3 && (PF) == 2 && (KSS) == 4)                                                                     \
@@ -974,10 +950,7 @@ void conv1_fwd_pool(uintptr_t x8, uintptr_t idx, uintptr_t w8, uintptr_t scale, 
   // the three dd rows of the 3^3 window unrolled: each row's pooling epilogue overlaps the next row's MFMAs and the
   // body needs 208 instead of 248 VGPRs (4.30 -> 4.17 ms per 64-client step, profiles/r3_ab_conv1_fwd_ddu.txt);
   // NIDT_C1_DDU=1 keeps the rolled loop (A/B)
-  static const int ddu = [] {
-    const char* e = getenv("NIDT_C1_DDU");
-    return e ? atoi(e) : 3;
-  }();
+  static const int ddu = env_int("NIDT_C1_DDU", 3);
   if (conv1_kslots() == 128 && ddu == 3 && pf == 2 && occ != 3 && conv1_tapord() == 0) {
     hipLaunchKernelGGL((k_conv1_fwd_pool_pipe<2, 4, 2, 3, 0>), dim3(kPD * NB * nq), dim3(256), 0, as_stream(stream),
                        ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
@@ -2175,39 +2148,24 @@ void conv1_wgrad(uintptr_t x8, uintptr_t idx, uintptr_t dp, uintptr_t pout, uint
   hipStream_t s = as_stream(stream);
   const int nq = conv1_wgrad_nq(NB);
   // NIDT_C1WG_UNROLL=2|4: unrolled cell loop (A/B: loads of the next cell overlap the current cell's FMAs)
-  static const int unr = [] {
-    const char* e = getenv("NIDT_C1WG_UNROLL");
-    return e ? atoi(e) : 1;
-  }();
+  static const int unr = env_int("NIDT_C1WG_UNROLL", 1);
   // NIDT_C1WG_DOT=1: the cell-paired bf16 dot-product kernel (A/B record: 4.52 ms vs 3.98 ms for this one at
   // 64 clients, profiles/r3_ab_conv1_wgrad_dot.txt — v_dot2c_f32_bf16 does not issue at the v_fma rate)
-  static const bool dot = [] {
-    const char* e = getenv("NIDT_C1WG_DOT");
-    return e && atoi(e) == 1;
-  }();
+  static const bool dot = env_int("NIDT_C1WG_DOT", 0) == 1;
 #define NIDT_C1WG(U)                                                                                                \
   hipLaunchKernelGGL(k_conv1_wgrad_split<U>, dim3(kPD * NB * nq), dim3(256), 0, s, ptr<const uint8_t>(x8),          \
                      ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout), ptr<const uint8_t>(amax), \
                      ptr<float>(part), nq)
-  static const int smf_env = [] {
-    const char* e = getenv("NIDT_C1WG_SMF");
-    return e ? atoi(e) : 0;
-  }();
+  static const int smf_env = env_int("NIDT_C1WG_SMF", 0);
   // NIDT_C1WG_MX=0 falls back from the argmax-row smfmac kernel (default) to the VALU gather
-  static const int mx_env = [] {
-    const char* e = getenv("NIDT_C1WG_MX");
-    return e ? atoi(e) : 1;
-  }();
+  static const int mx_env = env_int("NIDT_C1WG_MX", 1);
   const int mode = g_c1wg_mode >= 0 ? g_c1wg_mode : (smf_env == 1 ? 1 : mx_env == 1 ? 2 : 0);
   const bool smf = mode == 1;
   int nslab = B * kPD * nq;  // part slabs per client
   if (mode == 2) {
     const int npb = conv1_wgrad_mx_npb(NB), nblk = (kPD + npb - 1) / npb;
     NIDT_REQUIRE(nblk <= kPD * nq, "conv1_wgrad: part buffer");
-    static const int dbg = [] {
-      const char* e = getenv("NIDT_C1WG_DBG");
-      return e ? atoi(e) : 0;
-    }();
+    static const int dbg = env_int("NIDT_C1WG_DBG", 0);
     if (dbg)
       hipLaunchKernelGGL(k_conv1_wgrad_mx<1>, dim3(NB * nblk), dim3(512), 0, s, ptr<const uint8_t>(x8),
                          ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout),

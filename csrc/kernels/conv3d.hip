@@ -1110,6 +1110,38 @@ __global__ __launch_bounds__(1024) void k_fwd_splitk_fin(const float* __restrict
   }
 }
 
+// ---- runtime value -> template argument ----
+// Each helper calls the generic lambda f with std::integral_constant arguments, so the launchers below name a kernel
+// instantiation once, with typed arguments; `if constexpr` inside f marks the combinations that exist on purpose.
+template <class F>
+inline void dispatch_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// v must be one of Vs
+template <int... Vs, class F>
+inline void dispatch_int(int v, F&& f) {
+  const bool hit = ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+  NIDT_REQUIRE(hit, "dispatch_int: no kernel instantiation for value " + std::to_string(v));
+}
+
+// (BIAS, STATS) of the forward epilogues: the statistics need the bias path, so three states
+template <class F>
+inline void dispatch_epilogue(bool has_bias, bool has_stats, F&& f) {
+  if (has_stats) f(std::true_type{}, std::true_type{});
+  else if (has_bias) f(std::true_type{}, std::false_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+
+// output extent of one dimension: taps k (3 or 1), stride st, padding p
+static inline int conv_out_dim(int n, int k, int st, int p) { return (n + 2 * p - k) / st + 1; }
+// the stride-1 3-tap case, and the output positions per client of a stride-1 3x3(x3) conv
+static inline int conv_out_n(int n, int pad) { return n + 2 * pad - 2; }
+static inline int out_positions(int B, int D, int H, int W, int pad) {
+  return B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
+}
+
 int conv3d_fwd_bp(int Cin, int Cout, int xf, int G, int Mg);
 
 // launch one k_conv_fwd_dma variant; the 3-stage pipeline only where 3 LDS stages fit in 160 KB
@@ -1117,62 +1149,30 @@ int conv3d_fwd_bp(int Cin, int Cout, int xf, int G, int Mg);
 // the three A/Bs the same sign: 8-client step -0.6 %, 8-client round 15.25 -> 15.29 rounds/s, config 5 12.16 ->
 // 12.12 s/round; profiles/r4_ab_dma_sched.txt, r4_ab_sched_more.txt, r4_ab_dma_sched128.txt); 0 = off (A/B)
 static int dma_sched() {
-  static const int env = [] {
-    const char* e = getenv("NIDT_DMA_SCHED");
-    return e ? atoi(e) : 2;
-  }();
+  static const int env = env_int("NIDT_DMA_SCHED", 2);
   return env;
 }
 
 template <int BC, int WM, int WN, bool BI, bool ST>
 static void launch_fwd_dma(int nst, dim3 g, hipStream_t s, const ConvFwdArgs& a, int nCO) {
   constexpr int kStageBytes = (BC + 64 * WN) * 64 * 2;
-  if constexpr (BC == 64 && WM == 1) {
-    if (dma_sched()) {
-      if constexpr (3 * kStageBytes <= 160 * 1024) {
-        if (nst == 3) {
-          hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, 3, BI, ST, 1>), g, dim3(64 * WM * WN), 0, s, a, nCO);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, 2, BI, ST, 1>), g, dim3(64 * WM * WN), 0, s, a, nCO);
-      return;
-    }
-  }
-  if constexpr (BC == 128 && WM == 2) {
-    if (dma_sched() == 2) {
-      if constexpr (3 * kStageBytes <= 160 * 1024) {
-        if (nst == 3) {
-          hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, 3, BI, ST, 1>), g, dim3(64 * WM * WN), 0, s, a, nCO);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, 2, BI, ST, 1>), g, dim3(64 * WM * WN), 0, s, a, nCO);
-      return;
-    }
-  }
-  if constexpr (3 * kStageBytes <= 160 * 1024) {
-    if (nst == 3) {
-      hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, 3, BI, ST>), g, dim3(64 * WM * WN), 0, s, a, nCO);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, 2, BI, ST>), g, dim3(64 * WM * WN), 0, s, a, nCO);
+  const bool sched = BC == 64 ? dma_sched() != 0 : dma_sched() == 2;
+  dispatch_bool(sched, [&](auto sc) {
+    dispatch_bool(nst == 3, [&](auto three) {
+      constexpr int NST = (three.value && 3 * kStageBytes <= 160 * 1024) ? 3 : 2;
+      hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, NST, BI, ST, sc.value ? 1 : 0>), g, dim3(64 * WM * WN), 0, s, a,
+                         nCO);
+    });
+  });
 }
 
 // output channels per forward block: 128 (8 waves, one resident block per CU) where Cout allows, else 64 (4 waves,
 // two blocks per CU).  NIDT_FWD_BCO=64 forces 64-channel blocks everywhere (A/B).
 static int fwd_bco(int Cout) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_FWD_BCO");
-    return e ? atoi(e) : 0;
-  }();
+  static const int env = env_int("NIDT_FWD_BCO", 0);
   if (env == 64) return 64;
   return (Cout % 128 == 0) ? 128 : 64;
 }
-
-// output extent of one dimension: taps k (3 or 1), stride st, padding p
-static inline int conv_out_dim(int n, int k, int st, int p) { return (n + 2 * p - k) / st + 1; }
 
 struct PhasePlan;
 static void conv3d_fwd_impl(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t xs, uintptr_t xt, uintptr_t y,
@@ -1281,23 +1281,16 @@ static void conv3d_fwd_impl(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t 
     dim3 g1((unsigned)nwg);
     // small grids (64-position blocks: conv3-5 at 8 clients per GPU) run at ~1 wave per SIMD: a third LDS stage
     // keeps two k-steps of LDS-DMA in flight to cover the load latency the missing waves cannot hide.
-    static const int nst_env = [] {
-      const char* e = getenv("NIDT_FWD_NST");
-      return e ? atoi(e) : 0;
-    }();
+    static const int nst_env = env_int("NIDT_FWD_NST", 0);
     const int nst = nst_env ? nst_env : (bp == 64 ? 3 : 2);  // measured: 3 stages only pay with 64-position blocks
-#define NIDT_DMA(BC, WM, WN, BI, ST) launch_fwd_dma<BC, WM, WN, BI, ST>(nst, g1, s, a, nCO)
-#define NIDT_DMA_WN(WN)                                                                                     \
-    if (bco == 128) {                                                                                       \
-      if (st) NIDT_DMA(128, 2, WN, true, true); else if (hb) NIDT_DMA(128, 2, WN, true, false);             \
-      else NIDT_DMA(128, 2, WN, false, false);                                                              \
-    } else {                                                                                                \
-      if (st) NIDT_DMA(64, 1, WN, true, true); else if (hb) NIDT_DMA(64, 1, WN, true, false);               \
-      else NIDT_DMA(64, 1, WN, false, false);                                                               \
-    }
-    if (bp == 256) { NIDT_DMA_WN(4) } else if (bp == 512) { NIDT_DMA_WN(8) } else if (bp == 128) { NIDT_DMA_WN(2) } else { NIDT_DMA_WN(1) }
-#undef NIDT_DMA_WN
-#undef NIDT_DMA
+    dispatch_int<128, 64>(bco, [&](auto bc) {
+      dispatch_int<1, 2, 4, 8>(bp / 64, [&](auto wn) {  // one 64-position column of waves per 64 positions
+        dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
+          constexpr int BC = bc.value;
+          launch_fwd_dma<BC, BC / 64, wn.value, bi.value, sts.value>(nst, g1, s, a, nCO);
+        });
+      });
+    });
     NIDT_CHECK(hipGetLastError());
     if (a.ksplit > 1 && !hb && !st) {  // plain sum of the partial slabs -> bf16
       const int64_t n4 = (int64_t)G * a.Mg * Cout / 4;
@@ -1306,24 +1299,23 @@ static void conv3d_fwd_impl(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t 
       NIDT_CHECK(hipGetLastError());
     } else if (a.ksplit > 1) {
       const dim3 fg(a.nPB, G);
-      if (st) hipLaunchKernelGGL((k_fwd_splitk_fin<true, true>), fg, dim3(1024), 0, s, a.part, a.ksplit, a.bias, a.y, a.stats, G, a.Mg, Cout, bp, a.nPB, a.bias_ld ? a.bias_ld : (int64_t)Cout);
-      else if (hb) hipLaunchKernelGGL((k_fwd_splitk_fin<true, false>), fg, dim3(1024), 0, s, a.part, a.ksplit, a.bias, a.y, a.stats, G, a.Mg, Cout, bp, a.nPB, a.bias_ld ? a.bias_ld : (int64_t)Cout);
-      else hipLaunchKernelGGL((k_fwd_splitk_fin<false, false>), fg, dim3(1024), 0, s, a.part, a.ksplit, a.bias, a.y, a.stats, G, a.Mg, Cout, bp, a.nPB, a.bias_ld ? a.bias_ld : (int64_t)Cout);
+      dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
+        hipLaunchKernelGGL((k_fwd_splitk_fin<bi.value, sts.value>), fg, dim3(1024), 0, s, a.part, a.ksplit, a.bias, a.y,
+                           a.stats, G, a.Mg, Cout, bp, a.nPB, a.bias_ld ? a.bias_ld : (int64_t)Cout);
+      });
       NIDT_CHECK(hipGetLastError());
     }
     return;
   }
   NIDT_REQUIRE(ksplit <= 1, "conv3d_fwd: split-K needs the LDS-DMA path (Cin % 64 == 0, no input transform)");
   dim3 grid(a.nPB, Cout / bco, G);
-#define NIDT_FWD(BC, X, BI, ST) hipLaunchKernelGGL((k_conv_fwd<BC, X, BI, ST>), grid, dim3(256), 0, s, a)
-  if (bco == 128) {
-    if (xf) { if (st) NIDT_FWD(128, true, true, true); else if (hb) NIDT_FWD(128, true, true, false); else NIDT_FWD(128, true, false, false); }
-    else { if (st) NIDT_FWD(128, false, true, true); else if (hb) NIDT_FWD(128, false, true, false); else NIDT_FWD(128, false, false, false); }
-  } else {
-    if (xf) { if (st) NIDT_FWD(64, true, true, true); else if (hb) NIDT_FWD(64, true, true, false); else NIDT_FWD(64, true, false, false); }
-    else { if (st) NIDT_FWD(64, false, true, true); else if (hb) NIDT_FWD(64, false, true, false); else NIDT_FWD(64, false, false, false); }
-  }
-#undef NIDT_FWD
+  dispatch_int<128, 64>(bco, [&](auto bc) {
+    dispatch_bool(xf, [&](auto xfc) {
+      dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
+        hipLaunchKernelGGL((k_conv_fwd<bc.value, xfc.value, bi.value, sts.value>), grid, dim3(256), 0, s, a);
+      });
+    });
+  });
   NIDT_CHECK(hipGetLastError());
 }
 
@@ -1375,10 +1367,7 @@ void conv3d_fwd_bld(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, u
 // spatial size, few clients per GPU) but have long reductions get their k-steps split over ksplit blocks (>= 12
 // k-steps each), finished by k_fwd_splitk_sum.  NIDT_FWDG_KSPLIT=1 disables it (A/B), =k forces k.
 int conv_fwd_g_ksplit(int G, int B, int D, int H, int W, int Cin, int Cout, int kt, int st, int pad, int padd) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_FWDG_KSPLIT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int env = env_int("NIDT_FWDG_KSPLIT", 0);
   const int kd = kt == 27 ? 3 : 1, khw = kt == 1 ? 1 : 3;
   const int Mg = B * conv_out_dim(D, kd, st, padd) * conv_out_dim(H, khw, st, pad) * conv_out_dim(W, khw, st, pad);
   const int nks = kt * Cin / 64;
@@ -1420,10 +1409,7 @@ void conv3d_fwd_splitk(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, ui
 // profiles/r1_ab_fwd_splitk.txt), hence the < 256-block rule.  NIDT_FWD_KSPLIT=1 disables it, =k > 1 forces k.
 int conv3d_fwd_ksplit(int Cin, int Cout, int G, int Mg) {
   if (Cin % 64 != 0 || Cout > 256 || Cout % 64 != 0) return 1;
-  static const int env = [] {
-    const char* e = getenv("NIDT_FWD_KSPLIT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int env = env_int("NIDT_FWD_KSPLIT", 0);
   const int nks = 27 * Cin / 64;
   if (env == 1) return 1;
   if (env > 1) return std::max(1, std::min(env, nks / 8));
@@ -1438,75 +1424,97 @@ int conv3d_fwd_bp(int Cin, int Cout, int xf, int G, int Mg) {
   if (xf || Cin % 64 != 0) return kFwdBP;
   const int bco = fwd_bco(Cout);
   const int64_t nwg256 = (int64_t)ceil_div(Mg, 256) * (Cout / bco) * G;
-  static const int thresh = [] {
-    const char* e = getenv("NIDT_FWD_BP_THRESH");
-    return e ? atoi(e) : 256;
-  }();
+  static const int thresh = env_int("NIDT_FWD_BP_THRESH", 256);
   if (nwg256 < thresh) return 64;  // fewer blocks than CUs: 64-position blocks (measured: only then a win)
   // one 4-wave 64-channel block per CU (e.g. conv3-5 at 8 clients per GPU: 264 blocks): 128-position blocks of
   // 2 waves put two blocks on every CU instead
-  static const int bp128 = [] {
-    const char* e = getenv("NIDT_FWD_BP128");
-    return e ? atoi(e) : 1;
-  }();
+  static const int bp128 = env_int("NIDT_FWD_BP128", 1);
   if (bp128 && bco == 64 && nwg256 < 512) return 128;
   // large grids: 512-position blocks (16 waves for 128 channels, 160 KB of LDS) raise the MFMA work per byte of
   // LDS-DMA by 20 % and give each SIMD 4 waves.  NIDT_FWD_BP512=1 enables it (A/B).
-  static const int bp512 = [] {
-    const char* e = getenv("NIDT_FWD_BP512");
-    return e ? atoi(e) : 0;
-  }();
+  static const int bp512 = env_int("NIDT_FWD_BP512", 0);
   if (bp512 && nwg256 >= 4096) return 512;
   return 256;
 }
 
+// ---- union tables (k_union_table, below with the weight gradients): one description per kernel family ----
 static int union_umax(int B, int D, int H, int W, int pad, int P, int ext = 2);
 __global__ void k_union_table(int* tab, int U, int P, int Mg, int D, int H, int W, int pad, int ext);
 
+// P = output positions per band, U = union rows a band may hold (the kernel's template U; 0 = shape not eligible),
+// ext = rows a position reads past its base (2 = the three kw taps, 2 Wp + 2 = its whole window), threads = block
+// size of k_union_table
+struct UnionSpec {
+  int P, U, ext, threads;
+};
+
+static int union_table_size(const UnionSpec& u, int Mg, const char* who) {
+  NIDT_REQUIRE(u.U > 0, std::string(who) + ": shape not eligible");
+  return ceil_div(Mg, u.P) * (2 * u.U + u.P);
+}
+
+static void launch_union_table(const UnionSpec& u, const char* who, uintptr_t tab, int Mg, int D, int H, int W, int pad,
+                               uintptr_t stream) {
+  NIDT_REQUIRE(u.U > 0, std::string(who) + ": shape not eligible");
+  hipLaunchKernelGGL(k_union_table, dim3(ceil_div(Mg, u.P)), dim3(u.threads), 0, as_stream(stream), ptr<int>(tab), u.U,
+                     u.P, Mg, D, H, W, pad, u.ext);
+  NIDT_CHECK(hipGetLastError());
+}
+
+static inline bool extents_below_1024(int D, int H, int W, int pad) {
+  return D + 2 * pad < 1024 && H + 2 * pad < 1024 && W + 2 * pad < 1024;
+}
+
+// ConvFwdArgs of the stride-1 3x3(x3) family (k_conv_fwd_tri / _slab / _vol): kt taps, bp positions per block
+static ConvFwdArgs fwd_args_s1k3(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, uintptr_t y, uintptr_t stats,
+                                 int G, int B, int D, int H, int W, int Cin, int Cout, int pad, int kt, int bp) {
+  ConvFwdArgs a;
+  a.x = ptr<const uint16_t>(x); a.w = ptr<const uint16_t>(w); a.bias = ptr<const float>(bias);
+  a.xs = nullptr; a.xt = nullptr; a.y = ptr<uint16_t>(y); a.stats = ptr<float>(stats);
+  a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.pad = pad; a.padd = pad; a.kt = kt; a.st = 1;
+  a.Do = conv_out_n(D, pad); a.Ho = conv_out_n(H, pad); a.Wo = conv_out_n(W, pad);
+  a.Mg = B * a.Do * a.Ho * a.Wo;
+  a.nPB = ceil_div(a.Mg, bp);
+  a.G = G;
+  a.bias_ld = bias_ld;
+  return a;
+}
+
+// ---- k_conv_fwd_tri host side (union rows <= 320 / 384 per 256-position band) ----
 static inline int ft_ucap(int umax) { return umax <= 320 ? 320 : (umax <= 384 ? 384 : 0); }
+static UnionSpec fwd_tri_union(int B, int D, int H, int W, int pad) {
+  return {256, ft_ucap(union_umax(B, D, H, W, pad, 256)), 2, 256};
+}
 
 // k_conv_fwd_tri is used for this forward/dgrad (3x3x3 stride 1, 256-position blocks, union <= 384 rows, no split-K,
 // and measured faster for the shape): NIDT_FWD_TRI=0 turns it off (A/B against k_conv_fwd_dma)
 // the shape is supported by k_conv_fwd_tri (any client count; 256-position blocks)
 int conv3d_fwd_tri_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
   if (Cin % 64 != 0 || Cout % 64 != 0 || pad < 0 || pad > 2 || (int64_t)Cin * 27 > 27 * kMaxCin) return 0;
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
-  if (D + 2 * pad < 3 || H + 2 * pad < 3 || W + 2 * pad < 3 || Mg <= 0) return 0;
-  return ft_ucap(union_umax(B, D, H, W, pad, 256)) > 0 ? 1 : 0;
+  if (D + 2 * pad < 3 || H + 2 * pad < 3 || W + 2 * pad < 3 || out_positions(B, D, H, W, pad) <= 0) return 0;
+  return fwd_tri_union(B, D, H, W, pad).U > 0 ? 1 : 0;
 }
 
 int conv3d_fwd_tri_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_FWD_TRI");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = env_int("NIDT_FWD_TRI", 1);
   if (!env || !conv3d_fwd_tri_ok(B, D, H, W, Cin, Cout, pad)) return 0;
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
+  const int Mg = out_positions(B, D, H, W, pad);
   if (conv3d_fwd_bp(Cin, Cout, 0, G, Mg) != 256 || conv3d_fwd_ksplit(Cin, Cout, G, Mg) > 1) return 0;
-  const int U = ft_ucap(union_umax(B, D, H, W, pad, 256));
   // measured (profiles/r2_ab_fwd_tri.txt): conv2 fwd (unpadded) 3.25 -> 2.71 ms at 64 clients, 0.43 -> 0.34 at 8;
   // conv2 dgrad (pad 2, 320-row unions) 3.80 -> 3.67 on one box but 3.65 -> 3.68 on another (and 8-wave 64-channel
   // blocks 3.85), 0.48 -> 0.49 at 8 clients; the padded 5x7x5 convs (384-row unions) 5-25 % slower.  So: unpadded
   // convs only (the single union buffer's per-triplet reload is not hidden for the 4-wave 64-channel blocks).
-  (void)U;
   return pad == 0 ? 1 : 0;
 }
 
 int conv3d_fwd_tri_table_size(int B, int D, int H, int W, int pad) {
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
-  const int U = ft_ucap(union_umax(B, D, H, W, pad, 256));
-  NIDT_REQUIRE(U > 0, "conv3d_fwd_tri_table_size: shape not eligible");
-  return ceil_div(Mg, 256) * (2 * U + 256);
+  return union_table_size(fwd_tri_union(B, D, H, W, pad), out_positions(B, D, H, W, pad), "conv3d_fwd_tri_table_size");
 }
 
 void conv3d_fwd_tri_table(uintptr_t tab, int B, int D, int H, int W, int pad, uintptr_t stream) {
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
-  const int U = ft_ucap(union_umax(B, D, H, W, pad, 256));
-  NIDT_REQUIRE(U > 0, "conv3d_fwd_tri_table: shape not eligible");
-  NIDT_REQUIRE(D + 2 * pad < 1024 && H + 2 * pad < 1024 && W + 2 * pad < 1024, "conv3d_fwd_tri_table: extents < 1024");
-  hipLaunchKernelGGL(k_union_table, dim3(ceil_div(Mg, 256)), dim3(256), 0, as_stream(stream), ptr<int>(tab), U, 256, Mg,
-                     D, H, W, pad, 2);
-  NIDT_CHECK(hipGetLastError());
+  const UnionSpec u = fwd_tri_union(B, D, H, W, pad);
+  NIDT_REQUIRE(u.U == 0 || extents_below_1024(D, H, W, pad), "conv3d_fwd_tri_table: extents < 1024");
+  launch_union_table(u, "conv3d_fwd_tri_table", tab, out_positions(B, D, H, W, pad), D, H, W, pad, stream);
 }
 
 // forward (bias + BN block statistics optional; bias rows at stride bias_ld, 0 = Cout) through k_conv_fwd_tri
@@ -1516,31 +1524,22 @@ void conv3d_fwd_tri(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, u
   NIDT_REQUIRE((int64_t)B * D * H * W * Cin * 2 < (1ll << 31), "conv3d_fwd_tri: per-client input below 2 GiB");
   const bool hb = bias != 0, st = stats != 0;
   NIDT_REQUIRE(!st || hb, "conv3d_fwd_tri: statistics require a bias");
-  ConvFwdArgs a;
-  a.x = ptr<const uint16_t>(x); a.w = ptr<const uint16_t>(w); a.bias = ptr<const float>(bias);
-  a.xs = nullptr; a.xt = nullptr; a.y = ptr<uint16_t>(y); a.stats = ptr<float>(stats);
-  a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.pad = pad; a.padd = pad; a.kt = 27; a.st = 1;
-  a.Do = D + 2 * pad - 2; a.Ho = H + 2 * pad - 2; a.Wo = W + 2 * pad - 2;
-  a.Mg = B * a.Do * a.Ho * a.Wo;
-  a.nPB = ceil_div(a.Mg, 256);
-  a.G = G;
-  a.bias_ld = bias_ld;
-  const int U = ft_ucap(union_umax(B, D, H, W, pad, 256));
+  const ConvFwdArgs a = fwd_args_s1k3(x, w, bias, bias_ld, y, stats, G, B, D, H, W, Cin, Cout, pad, 27, 256);
   const int bco = fwd_bco(Cout), nCO = Cout / bco;
   const dim3 grid((unsigned)((int64_t)a.nPB * nCO * G));
   hipStream_t s = as_stream(stream);
   const int* tab = ptr<const int>(utab);
-#define NIDT_FT(BC, WM, UU, PD, BI, STT) \
-  hipLaunchKernelGGL((k_conv_fwd_tri<BC, WM, 4, UU, PD, BI, STT>), grid, dim3(256 * WM), 0, s, a, nCO, tab)
-#define NIDT_FT_B(BC, WM, UU, PD) \
-  if (st) NIDT_FT(BC, WM, UU, PD, true, true); else if (hb) NIDT_FT(BC, WM, UU, PD, true, false); else NIDT_FT(BC, WM, UU, PD, false, false);
-#define NIDT_FT_U(BC, WM)                                                                                        \
-  if (pad) { if (U == 320) { NIDT_FT_B(BC, WM, 320, true) } else { NIDT_FT_B(BC, WM, 384, true) } }             \
-  else { if (U == 320) { NIDT_FT_B(BC, WM, 320, false) } else { NIDT_FT_B(BC, WM, 384, false) } }
-  if (bco == 128) { NIDT_FT_U(128, 2) } else { NIDT_FT_U(64, 1) }
-#undef NIDT_FT_U
-#undef NIDT_FT_B
-#undef NIDT_FT
+  dispatch_int<128, 64>(bco, [&](auto bc) {
+    dispatch_int<320, 384>(fwd_tri_union(B, D, H, W, pad).U, [&](auto uu) {
+      dispatch_bool(pad != 0, [&](auto pd) {
+        dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
+          constexpr int BC = bc.value, WM = BC / 64;
+          hipLaunchKernelGGL((k_conv_fwd_tri<BC, WM, 4, uu.value, pd.value, bi.value, sts.value>), grid, dim3(256 * WM),
+                             0, s, a, nCO, tab);
+        });
+      });
+    });
+  });
   NIDT_CHECK(hipGetLastError());
 }
 
@@ -1554,15 +1553,17 @@ static inline int slab_u(int B, int D, int H, int W, int pad) {
   const int um = union_umax(B, D, H, W, pad, 256, slab_ext(W, pad));
   return um <= 384 ? 384 : (um <= 416 ? 416 : 0);
 }
+static UnionSpec fwd_slab_union(int B, int D, int H, int W, int pad) {
+  return {256, slab_u(B, D, H, W, pad), slab_ext(W, pad), 256};
+}
 
 // largest kd-slab union (rows) of a 256-position band: exposed for host-side tests of the slab rule
 int conv3d_slab_umax(int B, int D, int H, int W, int pad) { return union_umax(B, D, H, W, pad, 256, slab_ext(W, pad)); }
 
 int conv3d_fwd_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
   if (Cin % 64 != 0 || Cout % 64 != 0 || pad < 0 || pad > 2 || (int64_t)Cin * 27 > 27 * kMaxCin) return 0;
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
-  if (D + 2 * pad < 3 || H + 2 * pad < 3 || W + 2 * pad < 3 || Mg <= 0) return 0;
-  if (D + 2 * pad >= 1024 || H + 2 * pad >= 1024 || W + 2 * pad >= 1024) return 0;
+  if (D + 2 * pad < 3 || H + 2 * pad < 3 || W + 2 * pad < 3 || out_positions(B, D, H, W, pad) <= 0) return 0;
+  if (!extents_below_1024(D, H, W, pad)) return 0;
   const int U = slab_u(B, D, H, W, pad);
   return (U == 384 || (U == 416 && fwd_bco(Cout) == 64)) ? 1 : 0;
 }
@@ -1571,30 +1572,20 @@ int conv3d_fwd_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
 // against the per-tap kernel, conv2 fwd 2.65 -> 2.52 ms against k_conv_fwd_tri).  NIDT_FWD_SLAB=0 turns it off,
 // =1 keeps it to padded convs (A/B).
 int conv3d_fwd_slab_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_FWD_SLAB");
-    return e ? atoi(e) : 2;
-  }();
+  static const int env = env_int("NIDT_FWD_SLAB", 2);
   if (!env || !conv3d_fwd_slab_ok(B, D, H, W, Cin, Cout, pad)) return 0;
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
+  const int Mg = out_positions(B, D, H, W, pad);
   if (conv3d_fwd_bp(Cin, Cout, 0, G, Mg) != 256 || conv3d_fwd_ksplit(Cin, Cout, G, Mg) > 1) return 0;
   return (pad > 0 || env == 2) ? 1 : 0;
 }
 
 int conv3d_fwd_slab_table_size(int B, int D, int H, int W, int pad) {
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
-  const int U = slab_u(B, D, H, W, pad);
-  NIDT_REQUIRE(U > 0, "conv3d_fwd_slab_table_size: shape not eligible");
-  return ceil_div(Mg, 256) * (2 * U + 256);
+  return union_table_size(fwd_slab_union(B, D, H, W, pad), out_positions(B, D, H, W, pad), "conv3d_fwd_slab_table_size");
 }
 
 void conv3d_fwd_slab_table(uintptr_t tab, int B, int D, int H, int W, int pad, uintptr_t stream) {
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
-  const int U = slab_u(B, D, H, W, pad);
-  NIDT_REQUIRE(U > 0, "conv3d_fwd_slab_table: shape not eligible");
-  hipLaunchKernelGGL(k_union_table, dim3(ceil_div(Mg, 256)), dim3(256), 0, as_stream(stream), ptr<int>(tab), U, 256, Mg,
-                     D, H, W, pad, slab_ext(W, pad));
-  NIDT_CHECK(hipGetLastError());
+  launch_union_table(fwd_slab_union(B, D, H, W, pad), "conv3d_fwd_slab_table", tab, out_positions(B, D, H, W, pad), D, H,
+                     W, pad, stream);
 }
 
 static int slab_bd_u(int B, int H, int W, int bp = 256);
@@ -1609,19 +1600,9 @@ static void fwd_slab_impl(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias
   NIDT_REQUIRE((int64_t)B * D * H * W * Cin * 2 < (1ll << 31), "conv3d_fwd_slab: per-client input below 2 GiB");
   const bool hb = bias != 0, st = stats != 0;
   NIDT_REQUIRE(!st || hb, "conv3d_fwd_slab: statistics require a bias");
-  ConvFwdArgs a;
-  a.x = ptr<const uint16_t>(x); a.w = ptr<const uint16_t>(w); a.bias = ptr<const float>(bias);
-  a.xs = nullptr; a.xt = nullptr; a.y = ptr<uint16_t>(y); a.stats = ptr<float>(stats);
-  a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.pad = pad; a.padd = pad; a.kt = kt; a.st = 1;
-  a.Do = D + 2 * pad - 2; a.Ho = H + 2 * pad - 2; a.Wo = W + 2 * pad - 2;
-  a.Mg = B * a.Do * a.Ho * a.Wo;
-  a.nPB = ceil_div(a.Mg, bp);
-  a.G = G;
-  a.bias_ld = bias_ld;
-  static const int slab_dbg = [] {  // timing diagnostics only (wrong results): NIDT_SLAB_DBG=1 skips union reloads
-    const char* e = getenv("NIDT_SLAB_DBG");
-    return e ? atoi(e) : 0;
-  }();
+  ConvFwdArgs a = fwd_args_s1k3(x, w, bias, bias_ld, y, stats, G, B, D, H, W, Cin, Cout, pad, kt, bp);
+  // timing diagnostics only (wrong results): NIDT_SLAB_DBG=1 skips union reloads
+  static const int slab_dbg = env_int("NIDT_SLAB_DBG", 0);
   a.dbg = slab_dbg;
   a.kd1 = kd1;
   if (bp == 128) {  // [SLAB-BD] 128-position bands (4x4 maps: 8 padded samples = 288 union rows)
@@ -1636,49 +1617,43 @@ static void fwd_slab_impl(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias
   const dim3 grid((unsigned)((int64_t)a.nPB * nCO * G));
   hipStream_t s = as_stream(stream);
   const int* tab = ptr<const int>(utab);
-  static const int lswz = [] {  // NIDT_SLAB_LSWZ=1: output-space swizzle (A/B: no gain measured, see [LSWZ])
-    const char* e = getenv("NIDT_SLAB_LSWZ");
-    return e ? atoi(e) : 0;
-  }();
-  static const int na3 = [] {  // NIDT_SLAB_NA=3: three weight-tile stages for the 64-channel blocks (A/B)
-    const char* e = getenv("NIDT_SLAB_NA");
-    return e ? (atoi(e) == 3) : 0;
-  }();
+  // NIDT_SLAB_LSWZ=1: output-space swizzle (A/B: no gain measured, see [LSWZ])
+  static const int lswz = env_int("NIDT_SLAB_LSWZ", 0);
+  // NIDT_SLAB_NA=3: three weight-tile stages for the 64-channel blocks (A/B)
+  static const bool na3 = env_int("NIDT_SLAB_NA", 0) == 3;
   // [SCHED] fragment schedule for the 64-channel blocks (AlexNet conv2 data gradient 3.25 -> 3.00 ms at 64 clients,
   // profiles/r4_ab_slab_sched.txt; the 128-channel blocks would need > 128 VGPRs and lose their second block per CU:
   // conv2 forward 2.55 -> 3.23 ms).  NIDT_SLAB_SCHED=0: the compiler's schedule (A/B); =2 adds [SCHED-half] on the
   // 128-channel blocks (A/B)
-  static const int sched = [] {
-    const char* e = getenv("NIDT_SLAB_SCHED");
-    return e ? atoi(e) : 1;
-  }();
-#define NIDT_FS_U(BC, WM, UU, PD, BI, STT)                                                                        \
-  if (lswz) hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, UU, PD, BI, STT, true>), grid, dim3(256 * WM), 0, s, a,   \
-                               nCO, tab);                                                                          \
-  else if (na3 && BC == 64)                                                                                        \
-    hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, UU, PD, BI, STT, false, (BC == 64 ? 3 : 2)>), grid,            \
-                       dim3(256 * WM), 0, s, a, nCO, tab);                                                         \
-  else if (sched && BC == 64)                                                                                      \
-    hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, UU, PD, BI, STT, false, 2, (BC == 64 ? 1 : 0)>), grid,         \
-                       dim3(256 * WM), 0, s, a, nCO, tab);                                                         \
-  else if (sched == 2 && BC == 128 && !PD)                                                                         \
-    hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, UU, PD, BI, STT, false, 2, (BC == 128 && !PD ? 2 : 0)>), grid, \
-                       dim3(256 * WM), 0, s, a, nCO, tab);                                                         \
-  else hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, UU, PD, BI, STT, false>), grid, dim3(256 * WM), 0, s, a, nCO, tab)
-#define NIDT_FS_B(BC, WM, UU, PD)                                                                                  \
-  if (st) NIDT_FS_U(BC, WM, UU, PD, true, true); else if (hb) NIDT_FS_U(BC, WM, UU, PD, true, false);            \
-  else NIDT_FS_U(BC, WM, UU, PD, false, false);
+  static const int sched = env_int("NIDT_SLAB_SCHED", 1);
   // (8-wave 64-channel blocks, two 32-channel halves: conv2 data gradient 3.49 vs 3.25 ms — more VALU per MFMA from
   // the duplicated B addressing; profiles/r4_ab_slab_sched.txt, not kept)
-  if (bco == 128) {
-    if (pad) { NIDT_FS_B(128, 2, 384, true) } else { NIDT_FS_B(128, 2, 384, false) }
-  } else if (slab_u(B, D, H, W, pad) == 416) {
-    if (pad) { NIDT_FS_B(64, 1, 416, true) } else { NIDT_FS_B(64, 1, 416, false) }
-  } else {
-    if (pad) { NIDT_FS_B(64, 1, 384, true) } else { NIDT_FS_B(64, 1, 384, false) }
-  }
-#undef NIDT_FS_B
-#undef NIDT_FS_U
+  // the switches above as one kernel variant, first match wins: (LSW, NA, SCHED) template arguments
+  enum { kPlain, kLswz, kNa3, kSched, kSchedHalf };
+  const int variant = lswz ? kLswz
+                      : (na3 && bco == 64) ? kNa3
+                      : (sched && bco == 64) ? kSched
+                      : (sched == 2 && bco == 128 && !pad) ? kSchedHalf
+                      : kPlain;
+  dispatch_int<128, 64>(bco, [&](auto bc) {
+    dispatch_int<384, 416>(bco == 128 ? 384 : slab_u(B, D, H, W, pad), [&](auto uu) {
+      dispatch_bool(pad != 0, [&](auto pd) {
+        dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
+          dispatch_int<kPlain, kLswz, kNa3, kSched, kSchedHalf>(variant, [&](auto v) {
+            constexpr int BC = bc.value, WM = BC / 64, V = v.value;
+            constexpr bool PD = pd.value;
+            // 416-row unions, three weight stages and [SCHED] exist for the 64-channel blocks only, [SCHED-half] for
+            // the unpadded 128-channel blocks only
+            if constexpr ((BC == 64 || uu.value == 384) && (BC == 64 || (V != kNa3 && V != kSched)) &&
+                          (V != kSchedHalf || (BC == 128 && !PD)))
+              hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, uu.value, PD, bi.value, sts.value, V == kLswz,
+                                                  V == kNa3 ? 3 : 2, V == kSched ? 1 : (V == kSchedHalf ? 2 : 0)>),
+                                 grid, dim3(256 * WM), 0, s, a, nCO, tab);
+          });
+        });
+      });
+    });
+  });
   NIDT_CHECK(hipGetLastError());
 }
 
@@ -1700,10 +1675,7 @@ int conv2d_fwd_slab_ok(int B, int H, int W, int Cin, int Cout) {
 // slab's one-block-per-CU grid loses to the per-tap kernel's 64-position / split-K blocks: 1.09-1.56).
 // NIDT_2D_SLAB=0 turns it off, =2 forces it for every eligible shape (A/B).
 int conv2d_fwd_slab_pick(int G, int B, int H, int W, int Cin, int Cout) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_2D_SLAB");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = env_int("NIDT_2D_SLAB", 1);
   if (!env || !conv2d_fwd_slab_ok(B, H, W, Cin, Cout)) return 0;
   const int bco = fwd_bco(Cout);
   const int64_t blocks = (int64_t)ceil_div(B * H * W, 256) * (Cout / bco) * G;
@@ -1753,10 +1725,7 @@ int conv2d_fwd_slab_bd_ok(int B, int H, int W, int Cin, int Cout) { return slab_
 // (tools/bench_conv2d.py, profiles/r5_slab_bd.txt).
 // NIDT_2D_SLAB_BD=0 keeps the per-tap kernel (A/B)
 int conv2d_fwd_slab_bd_pick(int G, int B, int H, int W, int Cin, int Cout) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_2D_SLAB_BD");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = env_int("NIDT_2D_SLAB_BD", 1);
   const int bp = env ? slab_bd_bp(B, H, W, Cin, Cout) : 0;
   if (bp == 128) {  // one 8-wave block per band and 128 channels: small grids lose to the per-tap kernel's split-K
     // (4x4 maps at 10 clients x 16: 0.041 -> 0.062 ms; at 100 x 16: 0.193 -> 0.177; 100 x 62: 0.615 -> 0.548)
@@ -1768,24 +1737,19 @@ int conv2d_fwd_slab_bd_pick(int G, int B, int H, int W, int Cin, int Cout) {
 
 // union tables per (B, H, W, block positions): the caller passes the Cin / Cout of the layer so the same blocking is
 // chosen here and in conv2d_fwd_slab_bd
+// (bp = 0, a shape that is not eligible, gives U = 0)
+static UnionSpec slab_bd_union(int B, int H, int W, int bp) {
+  return {bp, bp > 0 ? slab_bd_u(B, H, W, bp) : 0, slab_ext(W, 1), 256};
+}
+
 int conv2d_fwd_slab_bd_table_size(int B, int H, int W, int Cin, int Cout) {
-  const int bp = slab_bd_bp(B, H, W, Cin, Cout);
-  NIDT_REQUIRE(bp > 0, "conv2d_fwd_slab_bd_table_size: shape not eligible");
-  if (bp == 256) return conv3d_fwd_slab_table_size(1, B, H, W, 1);
-  return ceil_div(B * H * W, 128) * (2 * 384 + 128);
+  return union_table_size(slab_bd_union(B, H, W, slab_bd_bp(B, H, W, Cin, Cout)), B * H * W,
+                          "conv2d_fwd_slab_bd_table_size");
 }
 
 void conv2d_fwd_slab_bd_table(uintptr_t tab, int B, int H, int W, int Cin, int Cout, uintptr_t stream) {
-  const int bp = slab_bd_bp(B, H, W, Cin, Cout);
-  NIDT_REQUIRE(bp > 0, "conv2d_fwd_slab_bd_table: shape not eligible");
-  if (bp == 256) {
-    conv3d_fwd_slab_table(tab, 1, B, H, W, 1, stream);
-    return;
-  }
-  const int Mg = B * H * W;
-  hipLaunchKernelGGL(k_union_table, dim3(ceil_div(Mg, 128)), dim3(256), 0, as_stream(stream), ptr<int>(tab), 384, 128,
-                     Mg, B, H, W, 1, slab_ext(W, 1));
-  NIDT_CHECK(hipGetLastError());
+  launch_union_table(slab_bd_union(B, H, W, slab_bd_bp(B, H, W, Cin, Cout)), "conv2d_fwd_slab_bd_table", tab, B * H * W,
+                     B, H, W, 1, stream);
 }
 
 void conv2d_fwd_slab_bd(uintptr_t x, uintptr_t w, uintptr_t y, int G, int B, int H, int W, int Cin, int Cout,
@@ -1808,16 +1772,10 @@ int conv3d_fwd_vol_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
 // 2.19 vs 1.71 ms per step: 3-wave blocks, one exposed weight-tile wait per tap) and within 1 % at 8 clients
 // (profiles/r3_ab_fwd_vol.txt).  When enabled: grids of >= NIDT_FWD_VOL_MINB (256) blocks without split-K.
 int conv3d_fwd_vol_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_FWD_VOL");
-    return e ? atoi(e) : 0;
-  }();
-  static const int minb = [] {
-    const char* e = getenv("NIDT_FWD_VOL_MINB");
-    return e ? atoi(e) : 256;
-  }();
+  static const int env = env_int("NIDT_FWD_VOL", 0);
+  static const int minb = env_int("NIDT_FWD_VOL_MINB", 256);
   if (!env || !conv3d_fwd_vol_ok(B, D, H, W, Cin, Cout, pad)) return 0;
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
+  const int Mg = out_positions(B, D, H, W, pad);
   if (conv3d_fwd_ksplit(Cin, Cout, G, Mg) > 1) return 0;
   return (int64_t)G * B * (Cout / 64) >= minb ? 1 : 0;
 }
@@ -1828,37 +1786,25 @@ void conv3d_fwd_vol(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, u
   NIDT_REQUIRE((int64_t)B * D * H * W * Cin * 2 < (1ll << 31), "conv3d_fwd_vol: per-client input below 2 GiB");
   const bool hb = bias != 0, st = stats != 0;
   NIDT_REQUIRE(!st || hb, "conv3d_fwd_vol: statistics require a bias");
-  ConvFwdArgs a;
-  a.x = ptr<const uint16_t>(x); a.w = ptr<const uint16_t>(w); a.bias = ptr<const float>(bias);
-  a.xs = nullptr; a.xt = nullptr; a.y = ptr<uint16_t>(y); a.stats = ptr<float>(stats);
-  a.B = B; a.D = D; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.pad = pad; a.padd = pad; a.kt = 27; a.st = 1;
-  a.Do = D + 2 * pad - 2; a.Ho = H + 2 * pad - 2; a.Wo = W + 2 * pad - 2;
-  a.Mg = B * a.Do * a.Ho * a.Wo;
+  ConvFwdArgs a = fwd_args_s1k3(x, w, bias, bias_ld, y, stats, G, B, D, H, W, Cin, Cout, pad, 27, 256);
   a.nPB = B;  // statistics blocks = samples
-  a.G = G;
-  a.bias_ld = bias_ld;
-  const int S = a.Do * a.Ho * a.Wo, wn = ceil_div(S, 64), nCO = Cout / 64;
-  static const int wm = [] {
-    const char* e = getenv("NIDT_FWD_VOL_WM");
-    return e ? atoi(e) : 1;
-  }();
+  const int S = a.Do * a.Ho * a.Wo, nCO = Cout / 64;
+  static const int wm = env_int("NIDT_FWD_VOL_WM", 1);
   const dim3 grid((unsigned)((int64_t)G * B * nCO));
   hipStream_t s = as_stream(stream);
-#define NIDT_FV(WM, WN, BI, STT) \
-  hipLaunchKernelGGL((k_conv_fwd_vol<64, WM, WN, kVolU, BI, STT>), grid, dim3(64 * WM * WN), 0, s, a, nCO)
-#define NIDT_FV_B(WM, WN) \
-  if (st) NIDT_FV(WM, WN, true, true); else if (hb) NIDT_FV(WM, WN, true, false); else NIDT_FV(WM, WN, false, false);
-#define NIDT_FV_N(WM) \
-  if (wn == 1) { NIDT_FV_B(WM, 1) } else if (wn == 2) { NIDT_FV_B(WM, 2) } else if (wn == 3) { NIDT_FV_B(WM, 3) } else { NIDT_FV_B(WM, 4) }
-  if (wm == 2) { NIDT_FV_N(2) } else { NIDT_FV_N(1) }
-#undef NIDT_FV_N
-#undef NIDT_FV_B
-#undef NIDT_FV
+  dispatch_int<1, 2>(wm == 2 ? 2 : 1, [&](auto wmc) {
+    dispatch_int<1, 2, 3, 4>(ceil_div(S, 64), [&](auto wn) {  // S <= 256 positions per sample
+      dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
+        hipLaunchKernelGGL((k_conv_fwd_vol<64, wmc.value, wn.value, kVolU, bi.value, sts.value>), grid,
+                           dim3(64 * wmc.value * wn.value), 0, s, a, nCO);
+      });
+    });
+  });
   NIDT_CHECK(hipGetLastError());
 }
 
 int conv3d_fwd_nblocks(int B, int D, int H, int W, int pad, int bp) {
-  const int Mg = B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2);
+  const int Mg = out_positions(B, D, H, W, pad);
   return ceil_div(Mg, bp);
 }
 
@@ -2053,10 +1999,7 @@ int wgrad1x1_chunks(int G, int64_t Mg, int N, int K);
 void wgrad1x1_g(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad, int64_t ldg, int64_t off, int G, int64_t Mg,
                 int N, int K, int nMB, float scale, uintptr_t stream);
 static bool wg1x1_on(int Cin, int Cout, int kt, int st) {
-  static const bool on = [] {
-    const char* e = getenv("NIDT_WG1X1");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_int("NIDT_WG1X1", 1) != 0;
   return on && kt == 1 && st == 1 && wgrad1x1_ok(Cout, Cin);
 }
 
@@ -2069,7 +2012,7 @@ static bool wg1x1_on(int Cin, int Cout, int kt, int st) {
 static int wgrad_nsplit_mk(int G, int Mg, int K, int Cout);
 
 int conv3d_wgrad_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  return wgrad_nsplit_mk(G, B * (D + 2 * pad - 2) * (H + 2 * pad - 2) * (W + 2 * pad - 2), 27 * Cin, Cout);
+  return wgrad_nsplit_mk(G, out_positions(B, D, H, W, pad), 27 * Cin, Cout);
 }
 
 int conv_wgrad_nsplit_g(int G, int B, int D, int H, int W, int Cin, int Cout, int kt, int st, int pad, int padd) {
@@ -2090,14 +2033,9 @@ static int wgrad_nsplit_mk(int G, int Mg, int K, int Cout) {
 // 64-position step per block slot and its fixed cost in steps
 static int wgrad_nsplit_base(int base, int G, int Mg, int K, int Cout, double step_us, double overhead_steps,
                              double slots) {
-  static const bool legacy = [] {
-    const char* e = getenv("NIDT_WG_NSPLIT_LEGACY");
-    return e && e[0] == '1';
-  }();
-  static const int force = [] {  // A/B experiments only: one split factor for every layer
-    const char* e = getenv("NIDT_WG_NSPLIT_FORCE");
-    return e ? atoi(e) : 0;
-  }();
+  static const bool legacy = env_int("NIDT_WG_NSPLIT_LEGACY", 0) == 1;
+  // A/B experiments only: one split factor for every layer
+  static const int force = env_int("NIDT_WG_NSPLIT_FORCE", 0);
   if (force > 0) return std::max(1, std::min(force, std::max(1, Mg / 64)));
   if (legacy) {
     const int ns = ceil_div(2048, base);
@@ -2801,27 +2739,20 @@ __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
   }
 }
 
-static inline int conv_out_n(int n, int pad) { return n + 2 * pad - 2; }
-
 // output channels per k_conv_wgrad_tri block: 64 (3 waves).  NIDT_WG_TRI_NCH=2 gives 128-channel blocks (6 waves)
 // where Cout allows (A/B: slower on every AlexNet layer, conv2 3.28 vs 3.06 ms at 64 clients,
 // profiles/r2_ab_wgrad_tri.txt)
 static int wt_nch(int Cout) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_WG_TRI_NCH");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = env_int("NIDT_WG_TRI_NCH", 1);
   return (Cout % 128 == 0 && env == 2) ? 2 : 1;
 }
 
 // split factor of k_conv_wgrad_tri: the wgrad cost model over its own tiles (9 x Cin/64 triplets x co blocks x G)
 int conv3d_wgrad_tri_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int ns_env = [] {  // NIDT_WG_TRI_NS=<n>: force the split of the unpadded (conv2) launch (A/B)
-    const char* e = getenv("NIDT_WG_TRI_NS");
-    return e ? atoi(e) : 0;
-  }();
+  // NIDT_WG_TRI_NS=<n>: force the split of the unpadded (conv2) launch (A/B)
+  static const int ns_env = env_int("NIDT_WG_TRI_NS", 0);
   if (ns_env > 0 && pad == 0) return ns_env;
-  const int Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
+  const int Mg = out_positions(B, D, H, W, pad);
   const int nch = wt_nch(Cout);
   // step cost ~1 us per block slot, no fixed term (128-channel blocks at 64 clients, conv2: ns 4 / 6 / 8 / 12 ->
   // 3.27 / 3.28 / 3.09 / 3.12 ms, profiles/r2_ab_wgrad_tri.txt)
@@ -2843,30 +2774,25 @@ int conv3d_wgrad_tri_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout
 }
 
 // step table for k_conv_wgrad_tri: ceil(Mg / 64) entries of 2U + 64 ints
+static UnionSpec wgrad_tri_union(int B, int D, int H, int W, int pad) {
+  return {64, wt_umax_cap(wgrad_tri_umax(B, D, H, W, pad)), 2, 64};
+}
+
 int conv3d_wgrad_tri_table_size(int B, int D, int H, int W, int pad) {
-  const int Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
-  const int U = wt_umax_cap(wgrad_tri_umax(B, D, H, W, pad));
-  NIDT_REQUIRE(U > 0, "conv3d_wgrad_tri_table_size: shape not eligible");
-  return ceil_div(Mg, 64) * (2 * U + 64);
+  return union_table_size(wgrad_tri_union(B, D, H, W, pad), out_positions(B, D, H, W, pad),
+                          "conv3d_wgrad_tri_table_size");
 }
 
 void conv3d_wgrad_tri_table(uintptr_t tab, int B, int D, int H, int W, int pad, uintptr_t stream) {
-  const int Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
-  const int U = wt_umax_cap(wgrad_tri_umax(B, D, H, W, pad));
-  NIDT_REQUIRE(U > 0, "conv3d_wgrad_tri_table: shape not eligible");
-  NIDT_REQUIRE(D + 2 * pad < 1024 && H + 2 * pad < 1024 && W + 2 * pad < 1024, "conv3d_wgrad_tri_table: extents < 1024");
-  hipLaunchKernelGGL(k_union_table, dim3(ceil_div(Mg, 64)), dim3(64), 0, as_stream(stream), ptr<int>(tab), U, 64, Mg,
-                     D, H, W, pad, 2);
-  NIDT_CHECK(hipGetLastError());
+  const UnionSpec u = wgrad_tri_union(B, D, H, W, pad);
+  NIDT_REQUIRE(u.U == 0 || extents_below_1024(D, H, W, pad), "conv3d_wgrad_tri_table: extents < 1024");
+  launch_union_table(u, "conv3d_wgrad_tri_table", tab, out_positions(B, D, H, W, pad), D, H, W, pad, stream);
 }
 
 // k_conv_wgrad_tri applies (3x3x3 stride 1, pad <= 2, 64-channel multiples, every step's union <= 96 rows) and is
 // not switched off (NIDT_WG_TRI=0 -> k_conv_wgrad_dma everywhere, A/B; NIDT_WG_TRI=2 -> only unpadded convs)
 int conv3d_wgrad_tri_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_WG_TRI");
-    return e ? atoi(e) : 1;
-  }();
+  static const int env = env_int("NIDT_WG_TRI", 1);
   if (!env || (env == 2 && pad != 0) || pad < 0 || pad > 2 || Cin % 64 != 0 || Cout % 64 != 0) return 0;
   if (conv_out_n(D, pad) < 1 || conv_out_n(H, pad) < 1 || conv_out_n(W, pad) < 1) return 0;
   return wt_umax_cap(wgrad_tri_umax(B, D, H, W, pad)) > 0 ? 1 : 0;
@@ -2879,12 +2805,32 @@ int conv3d_wgrad_tri_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) 
 // the threshold was 64 K before [ADMA]
 int conv3d_wgrad_tri_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
   if (!conv3d_wgrad_tri_ok(B, D, H, W, Cin, Cout, pad)) return 0;
-  static const int64_t minpos = [] {  // NIDT_WG_TRI_MINPOS: the padded-conv threshold (A/B)
-    const char* e = getenv("NIDT_WG_TRI_MINPOS");
-    return e ? (int64_t)atoll(e) : (int64_t)8192;
-  }();
-  const int64_t pos = (int64_t)G * B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
+  // NIDT_WG_TRI_MINPOS: the padded-conv threshold (A/B)
+  static const int64_t minpos = env_int64("NIDT_WG_TRI_MINPOS", 8192);
+  const int64_t pos = (int64_t)G * out_positions(B, D, H, W, pad);
   return (pad == 0 || pos >= minpos) ? 1 : 0;
+}
+
+// ConvWgTriArgs of the two union-staged weight gradients (k_conv_wgrad_tri / _slab): 64-position steps, nKT k tiles x
+// nCT channel tiles x nsplit splits x G clients; *nwg = the 1-D grid
+static ConvWgTriArgs wg_union_args(const char* who, uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t stab, int G,
+                                   int B, int D, int H, int W, int Cin, int Cout, int pad, int nsplit, int nKT, int nCT,
+                                   unsigned* nwg) {
+  ConvWgTriArgs d;
+  d.x = ptr<const uint16_t>(x); d.dy = ptr<const uint16_t>(dy); d.stab = ptr<const int>(stab); d.part = ptr<float>(part);
+  d.D = D; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.pad = pad;
+  d.Mg = out_positions(B, D, H, W, pad);
+  d.K = 27 * Cin; d.nsplit = nsplit; d.G = G;
+  d.chunk = ((ceil_div(d.Mg, nsplit) + 63) / 64) * 64;
+  d.nKT = nKT; d.nCT = nCT;
+  d.nstab = ceil_div(d.Mg, 64);
+  d.xclient = (int64_t)B * D * H * W * Cin;
+  NIDT_REQUIRE(d.xclient * 2 < (1ll << 31) && (int64_t)d.Mg * Cout * 2 < (1ll << 31),
+               std::string(who) + ": per-client tensors must stay below 2 GiB (32-bit buffer offsets)");
+  const int64_t n = (int64_t)d.nKT * d.nCT * nsplit * G;
+  NIDT_REQUIRE(n < (1ll << 31), std::string(who) + ": grid too large");
+  *nwg = (unsigned)n;
+  return d;
 }
 
 void conv3d_wgrad_tri(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad, int64_t ldg, int64_t off, int G, int B,
@@ -2892,74 +2838,53 @@ void conv3d_wgrad_tri(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad,
                       uintptr_t stream) {
   NIDT_REQUIRE(conv3d_wgrad_tri_ok(B, D, H, W, Cin, Cout, pad), "conv3d_wgrad_tri: shape not eligible");
   NIDT_REQUIRE(stab != 0 && nsplit >= 1, "conv3d_wgrad_tri: needs the step table");
-  const int U = wt_umax_cap(wgrad_tri_umax(B, D, H, W, pad));
-  ConvWgTriArgs d;
-  d.x = ptr<const uint16_t>(x); d.dy = ptr<const uint16_t>(dy); d.stab = ptr<const int>(stab); d.part = ptr<float>(part);
-  d.D = D; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.pad = pad;
-  d.Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
-  d.K = 27 * Cin; d.nsplit = nsplit; d.G = G;
-  d.chunk = ((ceil_div(d.Mg, nsplit) + 63) / 64) * 64;
   const int nch = wt_nch(Cout);
-  d.nKT = 9 * (Cin / 64); d.nCT = Cout / (64 * nch);
-  d.nstab = ceil_div(d.Mg, 64);
-  d.xclient = (int64_t)B * D * H * W * Cin;
-  NIDT_REQUIRE(d.xclient * 2 < (1ll << 31) && (int64_t)d.Mg * Cout * 2 < (1ll << 31),
-               "conv3d_wgrad_tri: per-client tensors must stay below 2 GiB (32-bit buffer offsets)");
-  const int64_t nwg = (int64_t)d.nKT * d.nCT * nsplit * G;
-  NIDT_REQUIRE(nwg < (1ll << 31), "conv3d_wgrad_tri: grid too large");
+  unsigned nwg;
+  const ConvWgTriArgs d = wg_union_args("conv3d_wgrad_tri", x, dy, part, stab, G, B, D, H, W, Cin, Cout, pad, nsplit,
+                                        9 * (Cin / 64), Cout / (64 * nch), &nwg);
   hipStream_t s = as_stream(stream);
-  const dim3 grid((unsigned)nwg);
-  static const int lsw_env = [] {  // NIDT_WGTRI_LSWZ=1: output-space swizzle of the X rows (A/B: slower, see [LSW])
-    const char* e = getenv("NIDT_WGTRI_LSWZ");
-    return e ? atoi(e) : 0;
-  }();
+  const dim3 grid(nwg);
+  // NIDT_WGTRI_LSWZ=1: output-space swizzle of the X rows (A/B: slower, see [LSW])
+  static const int lsw_env = env_int("NIDT_WGTRI_LSWZ", 0);
   const bool lsw = lsw_env && d.Mg / B >= 64;  // the kernel advances its output-space indices by 64 per step
   // [SCHED] k-step schedule (kstep_sched): AlexNet conv2-5 weight gradients at 64 clients 4.28 -> 4.24 ms
   // (profiles/r4_ab_sched_more.txt); NIDT_WGT_SCHED=0: the compiler's schedule (A/B)
-  static const int tsched = [] {
-    const char* e = getenv("NIDT_WGT_SCHED");
-    return e ? atoi(e) : 1;
-  }();
+  static const int tsched = env_int("NIDT_WGT_SCHED", 1);
   // [ADMA] asm-issued stage DMA (NIDT_WGT_ADMA=0: the intrinsic, A/B)
-  static const int tadma = [] {
-    const char* e = getenv("NIDT_WGT_ADMA");
-    return e ? atoi(e) : 1;
-  }();
-#define NIDT_TRI(NC, UU)                                                                                       \
-  if (tsched && !lsw && tadma) {                                                                               \
-    if (pad) hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, true, false, true, true>), grid, dim3(192 * NC), 0, s, d); \
-    else hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, false, false, true, true>), grid, dim3(192 * NC), 0, s, d); \
-  } else if (tsched && !lsw) {                                                                                        \
-    if (pad) hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, true, false, true>), grid, dim3(192 * NC), 0, s, d); \
-    else hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, false, false, true>), grid, dim3(192 * NC), 0, s, d);    \
-  } else if (lsw) {                                                                                            \
-    if (pad) hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, true, true>), grid, dim3(192 * NC), 0, s, d);        \
-    else hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, false, true>), grid, dim3(192 * NC), 0, s, d);           \
-  } else {                                                                                                     \
-    if (pad) hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, true, false>), grid, dim3(192 * NC), 0, s, d);       \
-    else hipLaunchKernelGGL((k_conv_wgrad_tri<NC, UU, false, false>), grid, dim3(192 * NC), 0, s, d);          \
-  }
-  if (nch == 2) {
-    if (U == 80) { NIDT_TRI(2, 80) } else { NIDT_TRI(2, 96) }
-  } else {
-    if (U == 80) { NIDT_TRI(1, 80) } else { NIDT_TRI(1, 96) }
-  }
-#undef NIDT_TRI
+  static const int tadma = env_int("NIDT_WGT_ADMA", 1);
+  // the output-space swizzle excludes the schedule, and the asm DMA exists with the schedule only
+  const bool sched = tsched && !lsw, adma = sched && tadma;
+  dispatch_int<1, 2>(nch, [&](auto nc) {
+    dispatch_int<80, 96>(wgrad_tri_union(B, D, H, W, pad).U, [&](auto uu) {
+      dispatch_bool(pad != 0, [&](auto pd) {
+        dispatch_bool(lsw, [&](auto lw) {
+          dispatch_bool(sched, [&](auto sc) {
+            dispatch_bool(adma, [&](auto ad) {
+              if constexpr (!(lw.value && sc.value) && (sc.value || !ad.value))
+                hipLaunchKernelGGL((k_conv_wgrad_tri<nc.value, uu.value, pd.value, lw.value, sc.value, ad.value>), grid,
+                                   dim3(192 * nc.value), 0, s, d);
+            });
+          });
+        });
+      });
+    });
+  });
   NIDT_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(Cout, G), dim3(256), 27 * (Cin + 1) * sizeof(float), s, ptr<const float>(part),
-                     nsplit, G, Cout, Cin, 27, ptr<float>(grad), ldg, off, scale);
-  NIDT_CHECK(hipGetLastError());
+  k_wgrad_reduce_launch(ptr<const float>(part), nsplit, G, Cout, Cin, 27, ptr<float>(grad), ldg, off, scale, s);
 }
 
 // ---- k_conv_wgrad_slab host side: 64-position steps, whole-window unions (ext = 2 Wp + 2) of <= 152 rows ----
 static inline int ws_u(int B, int D, int H, int W, int pad) {
   return union_umax(B, D, H, W, pad, 64, 2 * (W + 2 * pad) + 2) <= 152 ? 152 : 0;
 }
+static UnionSpec wgrad_slab_union(int B, int D, int H, int W, int pad) {
+  return {64, ws_u(B, D, H, W, pad), 2 * (W + 2 * pad) + 2, 64};
+}
 
 int conv3d_wgrad_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
   if (pad < 0 || pad > 2 || Cin % 64 != 0 || Cout % 64 != 0) return 0;
   if (conv_out_n(D, pad) < 1 || conv_out_n(H, pad) < 1 || conv_out_n(W, pad) < 1) return 0;
-  if (D + 2 * pad >= 1024 || H + 2 * pad >= 1024 || W + 2 * pad >= 1024) return 0;
+  if (!extents_below_1024(D, H, W, pad)) return 0;
   return ws_u(B, D, H, W, pad) > 0 ? 1 : 0;
 }
 
@@ -2968,34 +2893,25 @@ int conv3d_wgrad_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad)
 // (114 VGPRs) re-reads the dY tile from LDS in every wave and waits at each step's barrier with no second block
 // to cover it; the triplet kernel's two 3-wave blocks per CU overlap those waits.
 int conv3d_wgrad_slab_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = [] {
-    const char* e = getenv("NIDT_WG_SLAB");
-    return e ? atoi(e) : 0;
-  }();
+  static const int env = env_int("NIDT_WG_SLAB", 0);
   if (!env || !conv3d_wgrad_slab_ok(B, D, H, W, Cin, Cout, pad)) return 0;
   return conv3d_wgrad_tri_pick(G, B, D, H, W, Cin, Cout, pad) || env == 2 ? 1 : 0;
 }
 
 int conv3d_wgrad_slab_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  const int Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
+  const int Mg = out_positions(B, D, H, W, pad);
   // one 12-wave block per CU; ~3x the MFMAs of a k_conv_wgrad_tri step
   return wgrad_nsplit_base(G * (Cout / 64) * 3 * (Cin / 64), G, Mg, 27 * Cin, Cout, 1.5, 0.0, 256.0);
 }
 
 int conv3d_wgrad_slab_table_size(int B, int D, int H, int W, int pad) {
-  const int Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
-  const int U = ws_u(B, D, H, W, pad);
-  NIDT_REQUIRE(U > 0, "conv3d_wgrad_slab_table_size: shape not eligible");
-  return ceil_div(Mg, 64) * (2 * U + 64);
+  return union_table_size(wgrad_slab_union(B, D, H, W, pad), out_positions(B, D, H, W, pad),
+                          "conv3d_wgrad_slab_table_size");
 }
 
 void conv3d_wgrad_slab_table(uintptr_t tab, int B, int D, int H, int W, int pad, uintptr_t stream) {
-  const int Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
-  const int U = ws_u(B, D, H, W, pad);
-  NIDT_REQUIRE(U > 0, "conv3d_wgrad_slab_table: shape not eligible");
-  hipLaunchKernelGGL(k_union_table, dim3(ceil_div(Mg, 64)), dim3(64), 0, as_stream(stream), ptr<int>(tab), U, 64, Mg,
-                     D, H, W, pad, 2 * (W + 2 * pad) + 2);
-  NIDT_CHECK(hipGetLastError());
+  launch_union_table(wgrad_slab_union(B, D, H, W, pad), "conv3d_wgrad_slab_table", tab, out_positions(B, D, H, W, pad),
+                     D, H, W, pad, stream);
 }
 
 void conv3d_wgrad_slab(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad, int64_t ldg, int64_t off, int G,
@@ -3003,37 +2919,19 @@ void conv3d_wgrad_slab(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad
                        uintptr_t stream) {
   NIDT_REQUIRE(conv3d_wgrad_slab_ok(B, D, H, W, Cin, Cout, pad), "conv3d_wgrad_slab: shape not eligible");
   NIDT_REQUIRE(stab != 0 && nsplit >= 1, "conv3d_wgrad_slab: needs the step table");
-  ConvWgTriArgs d;
-  d.x = ptr<const uint16_t>(x); d.dy = ptr<const uint16_t>(dy); d.stab = ptr<const int>(stab); d.part = ptr<float>(part);
-  d.D = D; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.pad = pad;
-  d.Mg = B * conv_out_n(D, pad) * conv_out_n(H, pad) * conv_out_n(W, pad);
-  d.K = 27 * Cin; d.nsplit = nsplit; d.G = G;
-  d.chunk = ((ceil_div(d.Mg, nsplit) + 63) / 64) * 64;
-  d.nKT = 3 * (Cin / 64); d.nCT = Cout / 64;
-  d.nstab = ceil_div(d.Mg, 64);
-  d.xclient = (int64_t)B * D * H * W * Cin;
-  NIDT_REQUIRE(d.xclient * 2 < (1ll << 31) && (int64_t)d.Mg * Cout * 2 < (1ll << 31),
-               "conv3d_wgrad_slab: per-client tensors must stay below 2 GiB (32-bit buffer offsets)");
-  const int64_t nwg = (int64_t)d.nKT * d.nCT * nsplit * G;
-  NIDT_REQUIRE(nwg < (1ll << 31), "conv3d_wgrad_slab: grid too large");
+  unsigned nwg;
+  const ConvWgTriArgs d = wg_union_args("conv3d_wgrad_slab", x, dy, part, stab, G, B, D, H, W, Cin, Cout, pad, nsplit,
+                                        3 * (Cin / 64), Cout / 64, &nwg);
   hipStream_t s = as_stream(stream);
   // [ADMA] asm-issued stage DMA (k_conv_wgrad_tri); NIDT_WGS_ADMA=0: the intrinsic (A/B)
-  static const int sadma = [] {
-    const char* e = getenv("NIDT_WGS_ADMA");
-    return e ? atoi(e) : 1;
-  }();
-  if (sadma) {
-    if (pad) hipLaunchKernelGGL((k_conv_wgrad_slab<152, true, true>), dim3((unsigned)nwg), dim3(768), 0, s, d);
-    else hipLaunchKernelGGL((k_conv_wgrad_slab<152, false, true>), dim3((unsigned)nwg), dim3(768), 0, s, d);
-  } else if (pad) {
-    hipLaunchKernelGGL((k_conv_wgrad_slab<152, true>), dim3((unsigned)nwg), dim3(768), 0, s, d);
-  } else {
-    hipLaunchKernelGGL((k_conv_wgrad_slab<152, false>), dim3((unsigned)nwg), dim3(768), 0, s, d);
-  }
+  static const int sadma = env_int("NIDT_WGS_ADMA", 1);
+  dispatch_bool(pad != 0, [&](auto pd) {
+    dispatch_bool(sadma != 0, [&](auto ad) {
+      hipLaunchKernelGGL((k_conv_wgrad_slab<152, pd.value, ad.value>), dim3(nwg), dim3(768), 0, s, d);
+    });
+  });
   NIDT_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(Cout, G), dim3(256), 27 * (Cin + 1) * sizeof(float), s, ptr<const float>(part),
-                     nsplit, G, Cout, Cin, 27, ptr<float>(grad), ldg, off, scale);
-  NIDT_CHECK(hipGetLastError());
+  k_wgrad_reduce_launch(ptr<const float>(part), nsplit, G, Cout, Cin, 27, ptr<float>(grad), ldg, off, scale, s);
 }
 
 // positions table of a general conv (kt taps, stride st, h/w padding pad, depth padding padd): Mg = B*Do*Ho*Wo rows
@@ -3090,10 +2988,7 @@ static void conv_wgrad_impl(uintptr_t x, uintptr_t xs, uintptr_t xt, uintptr_t d
     // NIDT_WG_NCH=2: 128-channel blocks where Cout allows (8 waves, the X tile feeds both halves).  Measured slower
     // than two resident 64-channel blocks per CU (conv2 wgrad 3.91 -> 4.14 ms at 64 clients, 0.505 -> 0.542 ms
     // at 8; profiles/r2_ab_wgrad_nch.txt): the kernel is latency/barrier bound, not L2->LDS bandwidth bound.
-    static const int nch_env = [] {
-      const char* e = getenv("NIDT_WG_NCH");
-      return e ? atoi(e) : 0;
-    }();
+    static const int nch_env = env_int("NIDT_WG_NCH", 0);
     const int nch = (Cout % 128 == 0 && nch_env == 2) ? 2 : 1;
     d.nKT = ceil_div(a.K, kWgKC); d.nCT = Cout / (kWgCO * nch);
     d.xclient = (int64_t)B * D * H * W * Cin;
@@ -3102,10 +2997,7 @@ static void conv_wgrad_impl(uintptr_t x, uintptr_t xs, uintptr_t xt, uintptr_t d
     // scatters at a kt-float stride: CIFAR DisPFL (100 clients) -70 ms/round net, SubAvg (10 clients) +10 ms
     // (profiles/r5_pack_fuse_wg_direct.txt).  NIDT_WG_DIRECT=1 (default): 1x1 layers only (contiguous rows), 2: every layer,
     // 0: off (A/B; the results are bitwise equal either way)
-    static const int direct_env = [] {
-      const char* e = getenv("NIDT_WG_DIRECT");
-      return e ? atoi(e) : 1;
-    }();
+    static const int direct_env = env_int("NIDT_WG_DIRECT", 1);
     direct = nsplit == 1 && (direct_env == 2 || (direct_env == 1 && kt == 1));
     d.grad = direct ? ptr<float>(grad) : nullptr;
     d.ldg = ldg; d.off = off; d.scale = scale; d.kt = kt;
@@ -3115,37 +3007,25 @@ static void conv_wgrad_impl(uintptr_t x, uintptr_t xs, uintptr_t xt, uintptr_t d
     NIDT_REQUIRE(nwg < (1ll << 31), "conv3d_wgrad: grid too large");
     // [SCHED] k-step schedule (kstep_sched): AlexNet conv3-5 weight gradients at 8 clients -2.7 %, config 5 12.16 ->
     // 12.10 s/round (profiles/r4_ab_sched_more.txt); NIDT_WGD_SCHED=0: the compiler's schedule (A/B)
-    static const int wsched = [] {
-      const char* e = getenv("NIDT_WGD_SCHED");
-      return e ? atoi(e) : 1;
-    }();
+    static const int wsched = env_int("NIDT_WGD_SCHED", 1);
     // [ADMA] asm-issued stage DMA (k_conv_wgrad_tri); NIDT_WGD_ADMA=0: the intrinsic (A/B)
-    static const int wadma = [] {
-      const char* e = getenv("NIDT_WGD_ADMA");
-      return e ? atoi(e) : 1;
-    }();
-    if (wsched && wadma) {
-      if (nch == 2) hipLaunchKernelGGL((k_conv_wgrad_dma<2, true, true>), dim3((unsigned)nwg), dim3(512), 0, s, d);
-      else hipLaunchKernelGGL((k_conv_wgrad_dma<1, true, true>), dim3((unsigned)nwg), dim3(256), 0, s, d);
-    } else if (wsched) {
-      if (nch == 2) hipLaunchKernelGGL((k_conv_wgrad_dma<2, true>), dim3((unsigned)nwg), dim3(512), 0, s, d);
-      else hipLaunchKernelGGL((k_conv_wgrad_dma<1, true>), dim3((unsigned)nwg), dim3(256), 0, s, d);
-    } else if (nch == 2) {
-      hipLaunchKernelGGL(k_conv_wgrad_dma<2>, dim3((unsigned)nwg), dim3(512), 0, s, d);
-    } else {
-      hipLaunchKernelGGL(k_conv_wgrad_dma<1>, dim3((unsigned)nwg), dim3(256), 0, s, d);
-    }
+    static const int wadma = env_int("NIDT_WGD_ADMA", 1);
+    dispatch_int<1, 2>(nch, [&](auto nc) {
+      dispatch_bool(wsched != 0, [&](auto sc) {
+        dispatch_bool(wsched && wadma, [&](auto ad) {  // the asm DMA exists with the schedule only
+          if constexpr (sc.value || !ad.value)
+            hipLaunchKernelGGL((k_conv_wgrad_dma<nc.value, sc.value, ad.value>), dim3((unsigned)nwg),
+                               dim3(256 * nc.value), 0, s, d);
+        });
+      });
+    });
   } else {
     dim3 grid(ceil_div(a.K, kWgKC), Cout / kWgCO, G * nsplit);
-    if (xs) hipLaunchKernelGGL((k_conv_wgrad<true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_conv_wgrad<false>), grid, dim3(256), 0, s, a);
+    dispatch_bool(xs != 0, [&](auto xf) { hipLaunchKernelGGL((k_conv_wgrad<xf.value>), grid, dim3(256), 0, s, a); });
   }
   NIDT_CHECK(hipGetLastError());
   if (direct) return;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(Cout, G), dim3(256), kt * (Cin + 1) * sizeof(float), s,
-                     ptr<const float>(part), nsplit, G, Cout, Cin, kt,
-                     ptr<float>(grad), ldg, off, scale);
-  NIDT_CHECK(hipGetLastError());
+  k_wgrad_reduce_launch(ptr<const float>(part), nsplit, G, Cout, Cin, kt, ptr<float>(grad), ldg, off, scale, s);
 }
 
 void conv3d_wgrad(uintptr_t x, uintptr_t xs, uintptr_t xt, uintptr_t dy, uintptr_t part, uintptr_t grad, int64_t ldg,

@@ -769,10 +769,7 @@ void gn_bwd(uintptr_t dy, int dy_bf16, uintptr_t mask, uintptr_t t, uintptr_t st
   // [GN-REG] hold the bf16 dy in registers up to NIDT_GN_HOLD rows per thread (round 5: 4 — at 8 rows holding cost
   // the second resident block; round 6, with the ReLU masks no longer read here ([GN-RMASK], [OMASK]): 16, CIFAR SubAvg
   // +0.8 %, DisPFL +0.2 % vs 4, profiles/r6_gn_masks.txt)
-  static const int hold_max = [] {
-    const char* e = getenv("NIDT_GN_HOLD");
-    return e ? atoi(e) : 16;
-  }();
+  static const int hold_max = env_int("NIDT_GN_HOLD", 16);
   const bool hold = dy_bf16 && nv <= hold_max;
 #define GNB(NVV, DB, M)                                                                                        \
   if (DB && hold) hipLaunchKernelGGL((k_gn_bwd<NVV, DB, M, DB>), dim3(N), dim3(kGnThreads), 0, s,               \
@@ -898,10 +895,7 @@ void gn_bwd_rm(uintptr_t dy, int dy_bf16, uintptr_t t, uintptr_t stats, uintptr_
   NIDT_REQUIRE(!gn_streaming(S, C), "gn_bwd_rm: register-resident shapes only (gn_rm_ok)");
   hipStream_t s = as_stream(stream);
   const int nv = gn_nv(S, C);
-  static const int hold_max = [] {
-    const char* e = getenv("NIDT_GN_HOLD");
-    return e ? atoi(e) : 16;
-  }();
+  static const int hold_max = env_int("NIDT_GN_HOLD", 16);
   const bool hold = dy_bf16 && nv <= hold_max;
 #define GNR(NVV, DB, H)                                                                                        \
   hipLaunchKernelGGL((k_gn_bwd<NVV, DB, false, H, true>), dim3(N), dim3(kGnThreads), 0, s, ptr<const void>(dy), \

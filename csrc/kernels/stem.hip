@@ -741,10 +741,7 @@ void stem_bwd(uintptr_t dpool, uintptr_t amax, uintptr_t y, uintptr_t xq, uintpt
   const int nchunk = (d.OD + kWgOD - 1) / kWgOD;
   // [WG4] one block per (sample, od chunk) for all four jd (NIDT_STEM_WG4=0: k_stem_wgrad, A/B); its raw-row loads
   // are 8-byte words, so the polyphase rows must be a multiple of 8 bytes (64 at the ABCD shape)
-  static const bool wg4 = [] {
-    const char* e = getenv("NIDT_STEM_WG4");
-    return !(e && e[0] == '0');
-  }();
+  static const bool wg4 = env_int("NIDT_STEM_WG4", 1) != 0;
   if (wg4 && d.PX % 8 == 0)
     hipLaunchKernelGGL(k_stem_wgrad4, dim3(N * nchunk), dim3(512), 0, s, d, ptr<const uint8_t>(xq),
                        ptr<const uint16_t>(dz), ptr<const uint16_t>(y), ptr<const float>(coef), B, ptr<float>(slab));

@@ -137,3 +137,200 @@ def test_vol_kernel_rule():
     assert m.conv3d_fwd_vol_ok(16, 6, 8, 7, 64, 64, 1) == 0        # 8x10x9 = 720 padded rows
     assert m.conv3d_fwd_vol_ok(16, 5, 7, 5, 96, 128, 1) == 0       # channels not a multiple of 64
     assert m.conv3d_fwd_vol_pick(64, 16, 5, 7, 5, 128, 192, 1) == 0  # off unless NIDT_FWD_VOL=1
+
+
+# Host decisions of the conv launchers, recorded from the build before the launch dispatch was rewritten (default
+# environment: no NIDT_* switch set): function -> (arguments, result; a string = the call raises ValueError with that
+# text).  Shapes: the AlexNet3D conv2 / conv2 data gradient / conv3 / conv4 / conv5 geometries above at 1, 8 and 64
+# clients, the 31x37x31 layer-1 conv of the 3D ResNet at 1 and 8, and the ResNet-18-GN maps 32x32 (64 channels), 16x16
+# (128), 8x8 (256), 4x4 (512) and the Tiny 64x64 (64) at B = 16 and 10 / 100 clients.
+_PINNED = {
+    "conv3d_fwd_tri_ok": [
+        ((16, 19, 23, 19, 64, 128, 0), 1), ((16, 17, 21, 17, 128, 64, 2), 1), ((16, 5, 7, 5, 128, 192, 1), 1),
+        ((16, 5, 7, 5, 192, 192, 1), 1), ((16, 5, 7, 5, 192, 128, 1), 1), ((4, 31, 37, 31, 64, 64, 1), 1),
+    ],
+    "conv3d_fwd_slab_ok": [
+        ((16, 19, 23, 19, 64, 128, 0), 1), ((16, 17, 21, 17, 128, 64, 2), 1), ((16, 5, 7, 5, 128, 192, 1), 0),
+        ((16, 5, 7, 5, 192, 192, 1), 0), ((16, 5, 7, 5, 192, 128, 1), 0), ((4, 31, 37, 31, 64, 64, 1), 1),
+    ],
+    "conv3d_fwd_vol_ok": [
+        ((16, 19, 23, 19, 64, 128, 0), 0), ((16, 17, 21, 17, 128, 64, 2), 0), ((16, 5, 7, 5, 128, 192, 1), 1),
+        ((16, 5, 7, 5, 192, 192, 1), 1), ((16, 5, 7, 5, 192, 128, 1), 1), ((4, 31, 37, 31, 64, 64, 1), 0),
+    ],
+    "conv3d_wgrad_tri_ok": [
+        ((16, 19, 23, 19, 64, 128, 0), 1), ((16, 17, 21, 17, 128, 64, 2), 1), ((16, 5, 7, 5, 128, 192, 1), 1),
+        ((16, 5, 7, 5, 192, 192, 1), 1), ((16, 5, 7, 5, 192, 128, 1), 1), ((4, 31, 37, 31, 64, 64, 1), 1),
+    ],
+    "conv3d_wgrad_slab_ok": [
+        ((16, 19, 23, 19, 64, 128, 0), 1), ((16, 17, 21, 17, 128, 64, 2), 0), ((16, 5, 7, 5, 128, 192, 1), 1),
+        ((16, 5, 7, 5, 192, 192, 1), 1), ((16, 5, 7, 5, 192, 128, 1), 1), ((4, 31, 37, 31, 64, 64, 1), 0),
+    ],
+    "conv3d_fwd_tri_table_size": [
+        ((16, 19, 23, 19, 0), 340480), ((16, 17, 21, 17, 2), 465024), ((16, 5, 7, 5, 1), 11264),
+        ((4, 31, 37, 31, 1), 498176),
+    ],
+    "conv3d_fwd_slab_table_size": [
+        ((16, 19, 23, 19, 0), 389120), ((16, 17, 21, 17, 2), 531456),
+        ((16, 5, 7, 5, 1), 'nidt: conv3d_fwd_slab_table_size: shape not eligible'), ((4, 31, 37, 31, 1), 604928),
+        ((16, 1, 32, 32, 1), 65536), ((1, 16, 32, 32, 1), 65536), ((16, 1, 16, 16, 1), 16384),
+        ((1, 16, 16, 16, 1), 16384), ((16, 1, 8, 8, 1), 4352), ((1, 16, 8, 8, 1), 4352),
+        ((16, 1, 4, 4, 1), 'nidt: conv3d_fwd_slab_table_size: shape not eligible'),
+        ((1, 16, 4, 4, 1), 'nidt: conv3d_fwd_slab_table_size: shape not eligible'), ((16, 1, 64, 64, 1), 278528),
+        ((1, 16, 64, 64, 1), 278528),
+    ],
+    "conv3d_wgrad_tri_table_size": [
+        ((16, 19, 23, 19, 0), 340032), ((16, 17, 21, 17, 2), 465024), ((16, 5, 7, 5, 1), 11264),
+        ((4, 31, 37, 31, 1), 497952),
+    ],
+    "conv3d_wgrad_slab_table_size": [
+        ((16, 19, 23, 19, 0), 558624), ((16, 17, 21, 17, 2), 'nidt: conv3d_wgrad_slab_table_size: shape not eligible'),
+        ((16, 5, 7, 5, 1), 16192), ((4, 31, 37, 31, 1), 'nidt: conv3d_wgrad_slab_table_size: shape not eligible'),
+    ],
+    "conv3d_fwd_bp": [
+        ((64, 128, 0, 1, 97104), 256), ((64, 128, 0, 8, 97104), 256), ((64, 128, 0, 64, 97104), 256),
+        ((128, 64, 0, 1, 132848), 256), ((128, 64, 0, 8, 132848), 256), ((128, 64, 0, 64, 132848), 256),
+        ((128, 192, 0, 1, 2800), 64), ((128, 192, 0, 8, 2800), 128), ((128, 192, 0, 64, 2800), 256),
+        ((192, 192, 0, 1, 2800), 64), ((192, 192, 0, 8, 2800), 128), ((192, 192, 0, 64, 2800), 256),
+        ((192, 128, 0, 1, 2800), 64), ((192, 128, 0, 8, 2800), 64), ((192, 128, 0, 64, 2800), 256),
+        ((64, 64, 0, 1, 142228), 256), ((64, 64, 0, 8, 142228), 256), ((64, 64, 0, 10, 16384), 256),
+        ((64, 64, 0, 100, 16384), 256), ((128, 128, 0, 10, 4096), 64), ((128, 128, 0, 100, 4096), 256),
+        ((256, 256, 0, 10, 1024), 64), ((256, 256, 0, 100, 1024), 256), ((512, 512, 0, 10, 256), 64),
+        ((512, 512, 0, 100, 256), 256), ((64, 64, 0, 10, 65536), 256), ((64, 64, 0, 100, 65536), 256),
+    ],
+    "conv3d_fwd_ksplit": [
+        ((64, 128, 1, 97104), 1), ((64, 128, 8, 97104), 1), ((64, 128, 64, 97104), 1), ((128, 64, 1, 132848), 1),
+        ((128, 64, 8, 132848), 1), ((128, 64, 64, 132848), 1), ((128, 192, 1, 2800), 4), ((128, 192, 8, 2800), 1),
+        ((128, 192, 64, 2800), 1), ((192, 192, 1, 2800), 4), ((192, 192, 8, 2800), 1), ((192, 192, 64, 2800), 1),
+        ((192, 128, 1, 2800), 6), ((192, 128, 8, 2800), 1), ((192, 128, 64, 2800), 1), ((64, 64, 1, 142228), 1),
+        ((64, 64, 8, 142228), 1), ((64, 64, 10, 16384), 1), ((64, 64, 100, 16384), 1), ((128, 128, 10, 4096), 1),
+        ((128, 128, 100, 4096), 1), ((256, 256, 10, 1024), 1), ((256, 256, 100, 1024), 1), ((512, 512, 10, 256), 1),
+        ((512, 512, 100, 256), 1), ((64, 64, 10, 65536), 1), ((64, 64, 100, 65536), 1),
+    ],
+    "conv3d_fwd_tri_pick": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 1), ((8, 16, 19, 23, 19, 64, 128, 0), 1),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 1), ((1, 16, 17, 21, 17, 128, 64, 2), 0),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 0), ((64, 16, 17, 21, 17, 128, 64, 2), 0),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 0), ((64, 16, 5, 7, 5, 128, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 0), ((64, 16, 5, 7, 5, 192, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 0), ((8, 4, 31, 37, 31, 64, 64, 1), 0),
+    ],
+    "conv3d_fwd_slab_pick": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 1), ((8, 16, 19, 23, 19, 64, 128, 0), 1),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 1), ((1, 16, 17, 21, 17, 128, 64, 2), 1),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 1), ((64, 16, 17, 21, 17, 128, 64, 2), 1),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 0), ((64, 16, 5, 7, 5, 128, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 0), ((64, 16, 5, 7, 5, 192, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 1), ((8, 4, 31, 37, 31, 64, 64, 1), 1),
+    ],
+    "conv3d_fwd_vol_pick": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 0), ((8, 16, 19, 23, 19, 64, 128, 0), 0),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 0), ((1, 16, 17, 21, 17, 128, 64, 2), 0),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 0), ((64, 16, 17, 21, 17, 128, 64, 2), 0),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 0), ((64, 16, 5, 7, 5, 128, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 0), ((64, 16, 5, 7, 5, 192, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 0), ((8, 4, 31, 37, 31, 64, 64, 1), 0),
+    ],
+    "conv3d_wgrad_tri_pick": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 1), ((8, 16, 19, 23, 19, 64, 128, 0), 1),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 1), ((1, 16, 17, 21, 17, 128, 64, 2), 1),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 1), ((64, 16, 17, 21, 17, 128, 64, 2), 1),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 1), ((64, 16, 5, 7, 5, 128, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 1), ((64, 16, 5, 7, 5, 192, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 1), ((64, 16, 5, 7, 5, 192, 128, 1), 1),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 1), ((8, 4, 31, 37, 31, 64, 64, 1), 1),
+    ],
+    "conv3d_wgrad_tri_nsplit": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 64), ((8, 16, 19, 23, 19, 64, 128, 0), 22),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 7), ((1, 16, 17, 21, 17, 128, 64, 2), 55),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 7), ((64, 16, 17, 21, 17, 128, 64, 2), 8),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 5), ((8, 16, 5, 7, 5, 128, 192, 1), 2), ((64, 16, 5, 7, 5, 128, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 5), ((8, 16, 5, 7, 5, 192, 192, 1), 1), ((64, 16, 5, 7, 5, 192, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 5), ((8, 16, 5, 7, 5, 192, 128, 1), 2), ((64, 16, 5, 7, 5, 192, 128, 1), 1),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 64), ((8, 4, 31, 37, 31, 64, 64, 1), 14),
+    ],
+    "conv3d_wgrad_slab_pick": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 0), ((8, 16, 19, 23, 19, 64, 128, 0), 0),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 0), ((1, 16, 17, 21, 17, 128, 64, 2), 0),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 0), ((64, 16, 17, 21, 17, 128, 64, 2), 0),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 0), ((64, 16, 5, 7, 5, 128, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 0), ((64, 16, 5, 7, 5, 192, 192, 1), 0),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 0), ((8, 4, 31, 37, 31, 64, 64, 1), 0),
+    ],
+    "conv3d_wgrad_slab_nsplit": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 42), ((8, 16, 19, 23, 19, 64, 128, 0), 5),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 2), ((1, 16, 17, 21, 17, 128, 64, 2), 42),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 16), ((64, 16, 17, 21, 17, 128, 64, 2), 2),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 5), ((8, 16, 5, 7, 5, 128, 192, 1), 3), ((64, 16, 5, 7, 5, 128, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 5), ((8, 16, 5, 7, 5, 192, 192, 1), 1), ((64, 16, 5, 7, 5, 192, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 5), ((8, 16, 5, 7, 5, 192, 128, 1), 3), ((64, 16, 5, 7, 5, 192, 128, 1), 1),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 64), ((8, 4, 31, 37, 31, 64, 64, 1), 10),
+    ],
+    "conv3d_wgrad_nsplit": [
+        ((1, 16, 19, 23, 19, 64, 128, 0), 36), ((8, 16, 19, 23, 19, 64, 128, 0), 9),
+        ((64, 16, 19, 23, 19, 64, 128, 0), 4), ((1, 16, 17, 21, 17, 128, 64, 2), 36),
+        ((8, 16, 17, 21, 17, 128, 64, 2), 9), ((64, 16, 17, 21, 17, 128, 64, 2), 4),
+        ((1, 16, 5, 7, 5, 128, 192, 1), 5), ((8, 16, 5, 7, 5, 128, 192, 1), 1), ((64, 16, 5, 7, 5, 128, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 192, 1), 5), ((8, 16, 5, 7, 5, 192, 192, 1), 1), ((64, 16, 5, 7, 5, 192, 192, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 128, 1), 5), ((8, 16, 5, 7, 5, 192, 128, 1), 1), ((64, 16, 5, 7, 5, 192, 128, 1), 1),
+        ((1, 4, 31, 37, 31, 64, 64, 1), 64), ((8, 4, 31, 37, 31, 64, 64, 1), 9),
+    ],
+    "conv_wgrad_nsplit_g": [
+        ((1, 16, 19, 23, 19, 64, 128, 27, 1, 0, 0), 36), ((8, 16, 19, 23, 19, 64, 128, 27, 1, 0, 0), 9),
+        ((64, 16, 19, 23, 19, 64, 128, 27, 1, 0, 0), 4), ((1, 16, 17, 21, 17, 128, 64, 27, 1, 2, 2), 36),
+        ((8, 16, 17, 21, 17, 128, 64, 27, 1, 2, 2), 9), ((64, 16, 17, 21, 17, 128, 64, 27, 1, 2, 2), 4),
+        ((1, 16, 5, 7, 5, 128, 192, 27, 1, 1, 1), 5), ((8, 16, 5, 7, 5, 128, 192, 27, 1, 1, 1), 1),
+        ((64, 16, 5, 7, 5, 128, 192, 27, 1, 1, 1), 1), ((1, 16, 5, 7, 5, 192, 192, 27, 1, 1, 1), 5),
+        ((8, 16, 5, 7, 5, 192, 192, 27, 1, 1, 1), 1), ((64, 16, 5, 7, 5, 192, 192, 27, 1, 1, 1), 1),
+        ((1, 16, 5, 7, 5, 192, 128, 27, 1, 1, 1), 5), ((8, 16, 5, 7, 5, 192, 128, 27, 1, 1, 1), 1),
+        ((64, 16, 5, 7, 5, 192, 128, 27, 1, 1, 1), 1), ((1, 4, 31, 37, 31, 64, 64, 27, 1, 1, 1), 64),
+        ((8, 4, 31, 37, 31, 64, 64, 27, 1, 1, 1), 9), ((10, 16, 1, 32, 32, 64, 64, 9, 1, 1, 0), 16),
+        ((100, 16, 1, 32, 32, 64, 64, 9, 1, 1, 0), 3), ((10, 16, 1, 16, 16, 128, 128, 9, 1, 1, 0), 5),
+        ((100, 16, 1, 16, 16, 128, 128, 9, 1, 1, 0), 1), ((10, 16, 1, 8, 8, 256, 256, 9, 1, 1, 0), 1),
+        ((100, 16, 1, 8, 8, 256, 256, 9, 1, 1, 0), 1), ((10, 16, 1, 4, 4, 512, 512, 9, 1, 1, 0), 1),
+        ((100, 16, 1, 4, 4, 512, 512, 9, 1, 1, 0), 1), ((10, 16, 1, 64, 64, 64, 64, 9, 1, 1, 0), 17),
+        ((100, 16, 1, 64, 64, 64, 64, 9, 1, 1, 0), 5),
+    ],
+    "conv2d_fwd_slab_ok": [
+        ((16, 32, 32, 64, 64), 1), ((16, 16, 16, 128, 128), 1), ((16, 8, 8, 256, 256), 0), ((16, 4, 4, 512, 512), 0),
+        ((16, 64, 64, 64, 64), 1),
+    ],
+    "conv2d_fwd_slab_bd_ok": [
+        ((16, 32, 32, 64, 64), 0), ((16, 16, 16, 128, 128), 0), ((16, 8, 8, 256, 256), 1), ((16, 4, 4, 512, 512), 1),
+        ((16, 64, 64, 64, 64), 0),
+    ],
+    "conv2d_fwd_slab_bd_table_size": [
+        ((16, 32, 32, 64, 64), 'nidt: conv2d_fwd_slab_bd_table_size: shape not eligible'),
+        ((16, 16, 16, 128, 128), 'nidt: conv2d_fwd_slab_bd_table_size: shape not eligible'),
+        ((16, 8, 8, 256, 256), 4352), ((16, 4, 4, 512, 512), 1792),
+        ((16, 64, 64, 64, 64), 'nidt: conv2d_fwd_slab_bd_table_size: shape not eligible'),
+    ],
+    "conv2d_fwd_slab_pick": [
+        ((10, 16, 32, 32, 64, 64), 1), ((100, 16, 32, 32, 64, 64), 1), ((10, 16, 16, 16, 128, 128), 1),
+        ((100, 16, 16, 16, 128, 128), 1), ((10, 16, 8, 8, 256, 256), 0), ((100, 16, 8, 8, 256, 256), 0),
+        ((10, 16, 4, 4, 512, 512), 0), ((100, 16, 4, 4, 512, 512), 0), ((10, 16, 64, 64, 64, 64), 1),
+        ((100, 16, 64, 64, 64, 64), 1),
+    ],
+    "conv2d_fwd_slab_bd_pick": [
+        ((10, 16, 32, 32, 64, 64), 0), ((100, 16, 32, 32, 64, 64), 0), ((10, 16, 16, 16, 128, 128), 0),
+        ((100, 16, 16, 16, 128, 128), 0), ((10, 16, 8, 8, 256, 256), 1), ((100, 16, 8, 8, 256, 256), 1),
+        ((10, 16, 4, 4, 512, 512), 0), ((100, 16, 4, 4, 512, 512), 1), ((10, 16, 64, 64, 64, 64), 0),
+        ((100, 16, 64, 64, 64, 64), 0),
+    ],
+}
+
+
+def test_host_decisions_pinned():
+    m = _ext()
+    assert sum(len(v) for v in _PINNED.values()) == 308
+    for fn, cases in _PINNED.items():
+        for args, want in cases:
+            if isinstance(want, str):
+                with pytest.raises(ValueError) as err:
+                    getattr(m, fn)(*args)
+                assert str(err.value) == want, (fn, args)
+            else:
+                assert getattr(m, fn)(*args) == want, (fn, args)
