@@ -58,7 +58,6 @@ void conv3d_pos_table(uintptr_t tab, int B, int D, int H, int W, int pad, uintpt
 int conv3d_wgrad_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad);
 int conv3d_wgrad_tri_table_size(int B, int D, int H, int W, int pad);
 int conv3d_wgrad_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad);
-int conv3d_wgrad_slab_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad);
 int conv3d_wgrad_slab_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad);
 int conv3d_wgrad_slab_table_size(int B, int D, int H, int W, int pad);
 void conv3d_wgrad_slab_table(uintptr_t tab, int B, int D, int H, int W, int pad, uintptr_t stream);
@@ -71,10 +70,6 @@ int conv3d_fwd_tri_pick(int G, int B, int D, int H, int W, int Cin, int Cout, in
 int conv3d_fwd_tri_table_size(int B, int D, int H, int W, int pad);
 int conv3d_fwd_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad);
 int conv2d_fwd_slab_ok(int B, int H, int W, int Cin, int Cout);
-int conv3d_fwd_vol_ok(int B, int D, int H, int W, int Cin, int Cout, int pad);
-int conv3d_fwd_vol_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad);
-void conv3d_fwd_vol(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, uintptr_t y, uintptr_t stats, int G,
-                    int B, int D, int H, int W, int Cin, int Cout, int pad, uintptr_t stream);
 void unpack_bits_dev(uintptr_t bits, int64_t mstride, int64_t R, int64_t P, int f32, uintptr_t out, uintptr_t stream);
 void masked_rows(uintptr_t src, uintptr_t bits, int64_t mstride, int64_t C, int64_t P, int64_t ld, uintptr_t dst,
                  uintptr_t stream);
@@ -308,9 +303,6 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(conv3d_fwd_slab_table);
   DEF(conv3d_fwd_slab);
   DEF(conv2d_fwd_slab_ok);
-  DEF(conv3d_fwd_vol_ok);
-  DEF(conv3d_fwd_vol_pick);
-  DEF(conv3d_fwd_vol);
   DEF(unpack_bits_dev);
   DEF(masked_rows);
   DEF(stream_fork);
@@ -329,7 +321,6 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(conv3d_wgrad_tri_pick);
   DEF(conv3d_wgrad_tri);
   DEF(conv3d_wgrad_slab_ok);
-  DEF(conv3d_wgrad_slab_pick);
   DEF(conv3d_wgrad_slab_nsplit);
   DEF(conv3d_wgrad_slab_table_size);
   DEF(conv3d_wgrad_slab_table);

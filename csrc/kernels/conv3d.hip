@@ -58,7 +58,6 @@ struct ConvFwdArgs {
   int nph = 0, Dx = 0, Hx = 0, Wx = 0;
   unsigned char pnt[8] = {0}, pt0[8] = {0}, poff[8] = {0}, ptap[28] = {0};
   int kd1 = 0;          // k_conv_fwd_slab: depth tap kd = 1 only (2-D maps batched along depth, conv2d_fwd_slab_bd)
-  int dbg = 0;          // timing diagnostics only (NIDT_SLAB_DBG): 1 = k_conv_fwd_slab keeps its first union
 };
 
 constexpr int kFwdBP = 128;  // positions per block
@@ -358,29 +357,12 @@ __device__ __forceinline__ void kstep_sched(f32x4 (&acc)[TCO][TP], FA fa_at, FB 
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// [SCHED-half] the register-lean form for blocks at four waves per SIMD (<= 128 VGPRs): one 32-deep half's
-// fragments at a time, all of its reads ahead of its MFMAs
-template <int TCO, int TP, class FA, class FB>
-__device__ __forceinline__ void kstep_sched_half(f32x4 (&acc)[TCO][TP], FA fa_at, FB fb_at) {
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    bf16x8 fa[TCO], fb[TP];
-#pragma unroll
-    for (int i = 0; i < TCO; ++i) fa[i] = fa_at(kk, i);
-#pragma unroll
-    for (int j = 0; j < TP; ++j) fb[j] = fb_at(kk, j);
-#pragma unroll
-    for (int i = 0; i < TCO; ++i)
-#pragma unroll
-      for (int j = 0; j < TP; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, TCO + TP, 0);
-    __builtin_amdgcn_sched_group_barrier(0x8, TCO * TP, 0);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// [SCHED] on the forward blocks (dma_sched: NIDT_DMA_SCHED)
-template <int BCO, int WM, int WN, int NST, bool BIAS, bool STATS, int SCHED = 0>
+// [SCHED] on every forward block: the 64-channel blocks, then the 128-channel blocks too (each of the three A/Bs
+// the same sign: 8-client step -0.6 %, 8-client round 15.25 -> 15.29 rounds/s, config 5 12.16 -> 12.12 s/round;
+// profiles/r4_ab_dma_sched.txt, r4_ab_sched_more.txt, r4_ab_dma_sched128.txt).  Tried, lost: the compiler's own
+// schedule of this loop (same records); for the 5x7x5 conv3-5, a kernel staging each whole padded sample once for all
+// 27 taps (forward + data gradient 2.19 vs 1.71 ms per step at 64 clients, profiles/r3_ab_fwd_vol.txt)
+template <int BCO, int WM, int WN, int NST, bool BIAS, bool STATS>
 __global__ __launch_bounds__(64 * WM * WN, ((NST == 2 ? 8 : 4) / (WM * WN)) > 0 ? (NST == 2 ? 8 : 4) / (WM * WN) : 1) void k_conv_fwd_dma(ConvFwdArgs a, int nCO) {
   // waves: WM (co) x WN (positions); each wave owns (BCO/WM) co x 64 positions
   constexpr int NW = WM * WN, BP = 64 * WN, BK = 64;
@@ -507,30 +489,7 @@ __global__ __launch_bounds__(64 * WM * WN, ((NST == 2 ? 8 : 4) / (WM * WN)) > 0 
       const int r = wp * WP + j * 16 + fr;
       return *reinterpret_cast<const bf16x8*>(&sB[r * BK + (((4 * kk + fq) ^ swz_dma(r)) << 3)]);
     };
-    if constexpr (SCHED == 1) {
-      kstep_sched<TCO, TP>(acc, fa_at, fb_at);
-    } else if constexpr (SCHED == 2) {
-      kstep_sched_half<TCO, TP>(acc, fa_at, fb_at);
-    } else {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 fa[TCO], fb[TP];
-#pragma unroll
-      for (int i = 0; i < TCO; ++i) {
-        const int r = wco * WCO + i * 16 + fr;
-        fa[i] = *reinterpret_cast<const bf16x8*>(&sA[r * BK + (((4 * kk + fq) ^ swz_dma(r)) << 3)]);
-      }
-#pragma unroll
-      for (int j = 0; j < TP; ++j) {
-        const int r = wp * WP + j * 16 + fr;
-        fb[j] = *reinterpret_cast<const bf16x8*>(&sB[r * BK + (((4 * kk + fq) ^ swz_dma(r)) << 3)]);
-      }
-#pragma unroll
-      for (int i = 0; i < TCO; ++i)
-#pragma unroll
-        for (int j = 0; j < TP; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    }
+    kstep_sched<TCO, TP>(acc, fa_at, fb_at);
     // retire stage ks+1 (this wave's own glds), keep the younger stages in flight, then one barrier so
     // every wave's part of stage ks+1 has landed and every wave is done reading stage ks.
     {
@@ -708,23 +667,15 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_tri(ConvFwdArgs a,
 // per tap as in k_conv_fwd_tri; 256-position blocks and the k_conv_fwd_dma epilogue / statistics layout.  Depth taps
 // that read only padding for every position of a block (border output planes of the padded data gradient) are
 // skipped.  LDS: 48 KB union + 2 weight tiles (16 / 32 KB): two blocks per CU also at 128 output channels.
-// [LSWZ] the 16-B chunk swizzle of a union row is keyed by the row's output-space index L = (d Ho + h) Wo + w (its
-// padded coordinates of the kd = 0 union) instead of its union position u: the 16 positions of a B fragment read the
-// 16 CONSECUTIVE L values p + kh Wo + kw for every tap, across output-row and plane boundaries, where their union
-// positions jump by Wp - Wo + 1 (3 for a 3x3 window).  With the pair swizzle ((x >> 1) & 3) << 1 the rows of one
-// ds_read_b128 lane group then land on 16 distinct 4-bank slots; keyed by u, every fragment that crosses an output
-// row put two rows on one slot (modelled: 1.84 / 1.79 LDS cycles per B read for the AlexNet conv2 forward / data
-// gradient -> 1.00; measured 23-28 % LDS bank-conflict cycles, profiles/r3_s2_pmc_alexnet_g64.txt).  Measured
-// (profiles/r4_ab_lds_swizzle.txt): bank conflicts 23.4 / 28.3 % -> 0.1 %, but conv2 forward / data gradient time
-// unchanged (2.55 / 3.30 vs 2.55 / 3.25 ms) — the B reads are not what these blocks wait on.  Opt-in
-// (NIDT_SLAB_LSWZ=1); the union-position swizzle stays the default.
-__device__ __forceinline__ int swz_l(int l) { return ((l >> 1) & 3) << 1; }
-
-// [NA] weight-tile stages: 2 = double buffer (the tile of k-step ks + 1 lands under k-step ks), 3 = two tiles in
-// flight (the 64-channel blocks: 3 x 8 KB + the union still leave two blocks per CU).  Measured not faster (conv2
-// data gradient 3.32-3.35 vs 3.25 ms, profiles/r4_ab_slab_stages.txt): NA = 3 is opt-in (NIDT_SLAB_NA=3).
-template <int BCO, int WM, int WN, int U, bool PADDED, bool BIAS, bool STATS, bool LSW = true, int NA = 2,
-          int SCHED = 0>
+// The 64-channel blocks run the k-step under [SCHED] (kstep_sched: AlexNet conv2 data gradient 3.25 -> 3.00 ms at 64
+// clients, profiles/r4_ab_slab_sched.txt); the 128-channel blocks keep the compiler's schedule (with [SCHED] they need
+// > 128 VGPRs and lose their second block per CU: conv2 forward 2.55 -> 3.23 ms).
+// Tried, lost: a chunk swizzle keyed by the union row's output-space index (bank conflicts 23.4 / 28.3 % -> 0.1 %, conv2
+// forward / data gradient time unchanged, profiles/r4_ab_lds_swizzle.txt); three weight-tile stages for the 64-channel
+// blocks (conv2 data gradient 3.32-3.35 vs 3.25 ms, profiles/r4_ab_slab_stages.txt); 8-wave 64-channel blocks of two
+// 32-channel halves (3.49 vs 3.25 ms) and a register-lean half-step schedule on the 128-channel blocks
+// (profiles/r4_ab_slab_sched.txt).
+template <int BCO, int WM, int WN, int U, bool PADDED, bool BIAS, bool STATS>
 __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_slab(ConvFwdArgs a, int nCO, const int* __restrict__ utab) {
   constexpr int NW = WM * WN, BP = 64 * WN, BK = 64;
   constexpr int WCO = BCO / WM, WP = 64, TCO = WCO / 16, TP = WP / 16;
@@ -732,10 +683,9 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_slab(ConvFwdArgs a
   constexpr int A_INSTR = BCO / (8 * NW);
   constexpr int UP = U / 8, UPW = (UP + NW - 1) / NW;  // union pieces (8 rows) per wave
   static_assert(A_INSTR >= 1 && U % 8 == 0, "tile split");
-  static_assert(NA == 2 || NA == 3, "weight stages");
-  __shared__ __attribute__((aligned(16))) uint16_t smem[NA * A_ELEMS + U * BK];
+  __shared__ __attribute__((aligned(16))) uint16_t smem[2 * A_ELEMS + U * BK];
   uint16_t* const sAb = smem;
-  uint16_t* const sU = smem + NA * A_ELEMS;
+  uint16_t* const sU = smem + 2 * A_ELEMS;
 
   const int nwg = gridDim.x;
   const int id = xcd_remap(blockIdx.x, nwg);
@@ -768,19 +718,15 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_slab(ConvFwdArgs a
     uoff[i] = 0;
     ucode[i] = 1023;
     if (wid * UPW + i < UP) {
-      const int c = ent[2 * u + 1];
-      const int sw = LSW ? swz_l(((c & 1023) * a.Ho + ((c >> 10) & 1023)) * a.Wo + (c >> 20)) : swz_un(u);
-      uoff[i] = ent[2 * u] * (Cin * 2) + ((slot ^ sw) << 4);
-      ucode[i] = c;
+      uoff[i] = ent[2 * u] * (Cin * 2) + ((slot ^ swz_un(u)) << 4);
+      ucode[i] = ent[2 * u + 1];
     }
   }
-  int hrow[TP], hl[TP];  // union row and output-space index L of tap (0, 0) of each fragment position
-  const int So = a.Do * a.Ho * a.Wo;
+  int hrow[TP];  // union row of tap (0, 0) of each fragment position
 #pragma unroll
   for (int j = 0; j < TP; ++j) {
     const int pl = wp * WP + j * 16 + fr;
     hrow[j] = ent[2 * U + pl];
-    hl[j] = (pb * BP + pl) % So;
   }
   int aoff[A_INSTR];
 #pragma unroll
@@ -826,166 +772,27 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_slab(ConvFwdArgs a
 
   issue_u(q0);
   issue_a(0, 0);
-  if (NA == 3 && nks > 1) issue_a(1, 1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  int bcur = 0;  // buffer of k-step ks (ks % NA)
+  int bcur = 0;  // buffer of k-step ks (ks % 2)
   for (int ks = 0; ks < nks; ++ks) {
     const int ql = ks / 9, t = ks - 9 * ql, kh = t / 3, kw = t - 3 * kh;
-    const int bnext = bcur + 1 == NA ? 0 : bcur + 1;
-    if (NA == 2) {
-      if (ks + 1 < nks) issue_a(ks + 1, bnext);
-    } else if (ks + 2 < nks) {
-      issue_a(ks + 2, bnext + 1 == NA ? 0 : bnext + 1);
-    }
+    const int bnext = bcur + 1 == 2 ? 0 : bcur + 1;
+    if (ks + 1 < nks) issue_a(ks + 1, bnext);
     const uint16_t* sA = sAb + bcur * A_ELEMS;
     bcur = bnext;
-    const int toff = kh * Wp + kw, loff = kh * a.Wo + kw;
+    const int toff = kh * Wp + kw;
     auto fa_at = [&](int kk, int i) {
       const int r = wco * WCO + i * 16 + fr;
       return *reinterpret_cast<const bf16x8*>(&sA[r * BK + (((4 * kk + fq) ^ swz_dma(r)) << 3)]);
     };
     auto fb_at = [&](int kk, int j) {
       const int r = hrow[j] + toff;
-      const int sw = LSW ? swz_l(hl[j] + loff) : swz_un(r);
-      return *reinterpret_cast<const bf16x8*>(&sU[r * BK + (((4 * kk + fq) ^ sw) << 3)]);
+      return *reinterpret_cast<const bf16x8*>(&sU[r * BK + (((4 * kk + fq) ^ swz_un(r)) << 3)]);
     };
-    if constexpr (SCHED == 1) {  // [SCHED] (kstep_sched)
+    if constexpr (BCO == 64) {  // [SCHED] (kstep_sched)
       kstep_sched<TCO, TP>(acc, fa_at, fb_at);
-    } else if constexpr (SCHED == 2) {  // [SCHED-half]
-      kstep_sched_half<TCO, TP>(acc, fa_at, fb_at);
     } else {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 fa[TCO], fb[TP];
-#pragma unroll
-      for (int i = 0; i < TCO; ++i) {
-        const int r = wco * WCO + i * 16 + fr;
-        fa[i] = *reinterpret_cast<const bf16x8*>(&sA[r * BK + (((4 * kk + fq) ^ swz_dma(r)) << 3)]);
-      }
-#pragma unroll
-      for (int j = 0; j < TP; ++j) {
-        const int r = hrow[j] + toff;
-        const int sw = LSW ? swz_l(hl[j] + loff) : swz_un(r);
-        fb[j] = *reinterpret_cast<const bf16x8*>(&sU[r * BK + (((4 * kk + fq) ^ sw) << 3)]);
-      }
-#pragma unroll
-      for (int i = 0; i < TCO; ++i)
-#pragma unroll
-        for (int j = 0; j < TP; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    }
-    // the tile of k-step ks + 1 must have landed; with three stages the one of ks + 2 may stay in flight
-    if (NA == 3 && ks + 2 < nks) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(A_INSTR) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (t == 8 && ql + 1 < nq && a.dbg != 1) {  // every wave is done with this slab's union: reload it for the next one
-      issue_u(q0 + ql + 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-  }
-  __syncthreads();
-  conv_fwd_epilogue<BCO, BP, WM, WN, BIAS, STATS, TCO, TP>(a, acc, reinterpret_cast<float*>(smem), g, pb, co0, wco, wp, fr,
-                                                         fq, tid);
-}
-
-// k_conv_fwd_vol — 3x3x3 stride-1 forward/dgrad of small volumes (the AlexNet3D 5x7x5 conv3-5 layers) with the B
-// operand of a whole padded SAMPLE staged once per 64-channel chunk for all 27 taps.  Blocks are (sample, output-
-// channel chunk) with BP = 64 WN >= Do Ho Wo positions; the padded sample (Dp Hp Wp <= U rows, padding rows read out of
-// the buffer range as zeros) is the union of every tap's rows, so tap (kd, kh, kw) of output p reads union row
-// idx(p) + kd Hp Wp + kh Wp + kw — no table.  Against the per-tap kernel (one B tile per tap) this moves 27x fewer B
-// bytes per k-step; weights double-buffered per tap as in k_conv_fwd_slab.  Per-sample BN statistics blocks
-// (nPB = B, block size Do Ho Wo).
-template <int BCO, int WM, int WN, int U, bool BIAS, bool STATS>
-__global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_vol(ConvFwdArgs a, int nCO) {
-  constexpr int NW = WM * WN, BP = 64 * WN, BK = 64;
-  constexpr int WCO = BCO / WM, WP = 64, TCO = WCO / 16, TP = WP / 16;
-  constexpr int A_ELEMS = BCO * BK;
-  constexpr int AI = BCO / 8, AIW = (AI + NW - 1) / NW;   // weight-tile pieces (8 rows) and per wave
-  constexpr int UP = U / 8, UPW = (UP + NW - 1) / NW;     // union pieces and per wave
-  static_assert(U % 8 == 0 && TCO >= 1, "tile split");
-  __shared__ __attribute__((aligned(16))) uint16_t smem[2 * A_ELEMS + U * BK];
-  uint16_t* const sAb = smem;
-  uint16_t* const sU = smem + 2 * A_ELEMS;
-
-  const int nwg = gridDim.x;
-  const int id = xcd_remap(blockIdx.x, nwg);
-  const int cot = id % nCO, rest = id / nCO;
-  const int n = rest % a.B, g = rest / a.B;
-  const int co0 = cot * BCO;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wco = wid / WN, wp = wid % WN;
-  const int Cin = a.Cin, nck = Cin / BK, pad = a.pad;
-  const int Hp = a.H + 2 * pad, Wp = a.W + 2 * pad, HWp = Hp * Wp, R = (a.D + 2 * pad) * HWp;
-  const int S = a.Do * a.Ho * a.Wo, HoWo = a.Ho * a.Wo;
-  const int lrow = lane >> 3, slot = lane & 7;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int64_t vol = (int64_t)a.D * a.H * a.W;
-  // union pieces of this lane: padded row r -> source voxel of sample n (or out of range: zeros)
-  int uoff[UPW];
-#pragma unroll
-  for (int i = 0; i < UPW; ++i) {
-    const int u = 8 * (wid + NW * i) + lrow;
-    uoff[i] = kBufOOB;
-    if (wid + NW * i < UP && u < R) {
-      const int d = u / HWp - pad, h = (u / Wp) % Hp - pad, w = u % Wp - pad;
-      if ((unsigned)d < (unsigned)a.D && (unsigned)h < (unsigned)a.H && (unsigned)w < (unsigned)a.W)
-        uoff[i] = (int)(((n * vol + ((int64_t)d * a.H + h) * a.W + w) * Cin) * 2) + ((slot ^ swz_un(u)) << 4);
-    }
-  }
-  int hrow[TP];
-#pragma unroll
-  for (int j = 0; j < TP; ++j) {
-    int p = wp * WP + j * 16 + fr;
-    p = p < S ? p : 0;
-    const int od = p / HoWo, r2 = p - od * HoWo, oh = r2 / a.Wo, ow = r2 - oh * a.Wo;
-    hrow[j] = od * HWp + oh * Wp + ow;
-  }
-  int aoff[AIW];
-#pragma unroll
-  for (int i = 0; i < AIW; ++i) {
-    const int row = 8 * (wid + NW * i) + lrow;
-    aoff[i] = ((co0 + row) * 27 * Cin + ((slot ^ swz_dma(row)) << 3)) * 2;
-  }
-  const int64_t xcl = (int64_t)a.B * vol * Cin;
-  const i32x4_t rxs = make_rsrc(a.x + (int64_t)g * xcl, (uint32_t)(xcl * 2));
-  const i32x4_t rws = make_rsrc(a.w + (int64_t)g * a.Cout * 27 * Cin, (uint32_t)(a.Cout * 27 * Cin * 2));
-
-  auto issue_a = [&](int ks, int buf) {  // weight tile of tap t = ks % 27 of channel chunk ks / 27
-    const int cc = ks / 27, t = ks - 27 * cc;
-    const int woff = (t * Cin + cc * BK) * 2;
-    uint16_t* sA = sAb + buf * A_ELEMS;
-#pragma unroll
-    for (int i = 0; i < AIW; ++i)
-      if (wid + NW * i < AI) blds16(rws, aoff[i] + woff, sA + (wid + NW * i) * 512);
-  };
-  auto issue_u = [&](int cc) {
-#pragma unroll
-    for (int i = 0; i < UPW; ++i) {
-      if (wid + NW * i >= UP) continue;
-      const int o = uoff[i];
-      blds16(rxs, o == kBufOOB ? kBufOOB : o + cc * (BK * 2), sU + (wid + NW * i) * 512);
-    }
-  };
-
-  f32x4 acc[TCO][TP];
-#pragma unroll
-  for (int i = 0; i < TCO; ++i)
-#pragma unroll
-    for (int j = 0; j < TP; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nks = 27 * nck;
-  issue_u(0);
-  issue_a(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  for (int ks = 0; ks < nks; ++ks) {
-    const int cc = ks / 27, t = ks - 27 * cc, kd = t / 9, kh = (t / 3) % 3, kw = t % 3;
-    if (ks + 1 < nks) issue_a(ks + 1, (ks + 1) & 1);
-    const uint16_t* sA = sAb + (ks & 1) * A_ELEMS;
-    const int toff = kd * HWp + kh * Wp + kw;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 fa[TCO], fb[TP];
@@ -1004,17 +811,18 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void k_conv_fwd_vol(ConvFwdArgs a,
 #pragma unroll
         for (int j = 0; j < TP; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // the tile of k-step ks + 1 must have landed
     __builtin_amdgcn_s_barrier();
-    if (t == 26 && cc + 1 < nck) {  // every wave is done with this chunk's union: reload it for the next one
-      issue_u(cc + 1);
+    if (t == 8 && ql + 1 < nq) {  // every wave is done with this slab's union: reload it for the next one
+      issue_u(q0 + ql + 1);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
   }
   __syncthreads();
-  conv_fwd_epilogue<BCO, BP, WM, WN, BIAS, STATS, TCO, TP>(a, acc, reinterpret_cast<float*>(smem), g, n, co0, wco, wp, fr,
-                                                         fq, tid, 0, n * S, n * S + S);
+  conv_fwd_epilogue<BCO, BP, WM, WN, BIAS, STATS, TCO, TP>(a, acc, reinterpret_cast<float*>(smem), g, pb, co0, wco, wp, fr,
+                                                         fq, tid);
 }
 
 // Finish of a split-K forward without bias / statistics: y = bf16(sum over the ksplit slabs), 4 values per thread
@@ -1145,34 +953,18 @@ static inline int out_positions(int B, int D, int H, int W, int pad) {
 int conv3d_fwd_bp(int Cin, int Cout, int xf, int G, int Mg);
 
 // launch one k_conv_fwd_dma variant; the 3-stage pipeline only where 3 LDS stages fit in 160 KB
-// [SCHED] on the per-tap forward blocks: 1 = the 64-channel blocks, 2 (default) = the 128-channel blocks too (each of
-// the three A/Bs the same sign: 8-client step -0.6 %, 8-client round 15.25 -> 15.29 rounds/s, config 5 12.16 ->
-// 12.12 s/round; profiles/r4_ab_dma_sched.txt, r4_ab_sched_more.txt, r4_ab_dma_sched128.txt); 0 = off (A/B)
-static int dma_sched() {
-  static const int env = env_int("NIDT_DMA_SCHED", 2);
-  return env;
-}
-
 template <int BC, int WM, int WN, bool BI, bool ST>
 static void launch_fwd_dma(int nst, dim3 g, hipStream_t s, const ConvFwdArgs& a, int nCO) {
   constexpr int kStageBytes = (BC + 64 * WN) * 64 * 2;
-  const bool sched = BC == 64 ? dma_sched() != 0 : dma_sched() == 2;
-  dispatch_bool(sched, [&](auto sc) {
-    dispatch_bool(nst == 3, [&](auto three) {
-      constexpr int NST = (three.value && 3 * kStageBytes <= 160 * 1024) ? 3 : 2;
-      hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, NST, BI, ST, sc.value ? 1 : 0>), g, dim3(64 * WM * WN), 0, s, a,
-                         nCO);
-    });
+  dispatch_bool(nst == 3, [&](auto three) {
+    constexpr int NST = (three.value && 3 * kStageBytes <= 160 * 1024) ? 3 : 2;
+    hipLaunchKernelGGL((k_conv_fwd_dma<BC, WM, WN, NST, BI, ST>), g, dim3(64 * WM * WN), 0, s, a, nCO);
   });
 }
 
 // output channels per forward block: 128 (8 waves, one resident block per CU) where Cout allows, else 64 (4 waves,
-// two blocks per CU).  NIDT_FWD_BCO=64 forces 64-channel blocks everywhere (A/B).
-static int fwd_bco(int Cout) {
-  static const int env = env_int("NIDT_FWD_BCO", 0);
-  if (env == 64) return 64;
-  return (Cout % 128 == 0) ? 128 : 64;
-}
+// two blocks per CU; tried, lost: 64-channel blocks everywhere, profiles/r2_ab_fwd_bco.txt)
+static int fwd_bco(int Cout) { return (Cout % 128 == 0) ? 128 : 64; }
 
 struct PhasePlan;
 static void conv3d_fwd_impl(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t xs, uintptr_t xt, uintptr_t y,
@@ -1281,10 +1073,9 @@ static void conv3d_fwd_impl(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t 
     dim3 g1((unsigned)nwg);
     // small grids (64-position blocks: conv3-5 at 8 clients per GPU) run at ~1 wave per SIMD: a third LDS stage
     // keeps two k-steps of LDS-DMA in flight to cover the load latency the missing waves cannot hide.
-    static const int nst_env = env_int("NIDT_FWD_NST", 0);
-    const int nst = nst_env ? nst_env : (bp == 64 ? 3 : 2);  // measured: 3 stages only pay with 64-position blocks
+    const int nst = bp == 64 ? 3 : 2;  // measured: 3 stages only pay with 64-position blocks
     dispatch_int<128, 64>(bco, [&](auto bc) {
-      dispatch_int<1, 2, 4, 8>(bp / 64, [&](auto wn) {  // one 64-position column of waves per 64 positions
+      dispatch_int<1, 2, 4>(bp / 64, [&](auto wn) {  // one 64-position column of waves per 64 positions
         dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
           constexpr int BC = bc.value;
           launch_fwd_dma<BC, BC / 64, wn.value, bi.value, sts.value>(nst, g1, s, a, nCO);
@@ -1430,10 +1221,7 @@ int conv3d_fwd_bp(int Cin, int Cout, int xf, int G, int Mg) {
   // 2 waves put two blocks on every CU instead
   static const int bp128 = env_int("NIDT_FWD_BP128", 1);
   if (bp128 && bco == 64 && nwg256 < 512) return 128;
-  // large grids: 512-position blocks (16 waves for 128 channels, 160 KB of LDS) raise the MFMA work per byte of
-  // LDS-DMA by 20 % and give each SIMD 4 waves.  NIDT_FWD_BP512=1 enables it (A/B).
-  static const int bp512 = env_int("NIDT_FWD_BP512", 0);
-  if (bp512 && nwg256 >= 4096) return 512;
+  // (tried, lost: 512-position blocks for large grids, profiles/r1_ab_fwd_bp512.txt)
   return 256;
 }
 
@@ -1465,7 +1253,7 @@ static inline bool extents_below_1024(int D, int H, int W, int pad) {
   return D + 2 * pad < 1024 && H + 2 * pad < 1024 && W + 2 * pad < 1024;
 }
 
-// ConvFwdArgs of the stride-1 3x3(x3) family (k_conv_fwd_tri / _slab / _vol): kt taps, bp positions per block
+// ConvFwdArgs of the stride-1 3x3(x3) family (k_conv_fwd_tri / _slab): kt taps, bp positions per block
 static ConvFwdArgs fwd_args_s1k3(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, uintptr_t y, uintptr_t stats,
                                  int G, int B, int D, int H, int W, int Cin, int Cout, int pad, int kt, int bp) {
   ConvFwdArgs a;
@@ -1601,14 +1389,11 @@ static void fwd_slab_impl(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias
   const bool hb = bias != 0, st = stats != 0;
   NIDT_REQUIRE(!st || hb, "conv3d_fwd_slab: statistics require a bias");
   ConvFwdArgs a = fwd_args_s1k3(x, w, bias, bias_ld, y, stats, G, B, D, H, W, Cin, Cout, pad, kt, bp);
-  // timing diagnostics only (wrong results): NIDT_SLAB_DBG=1 skips union reloads
-  static const int slab_dbg = env_int("NIDT_SLAB_DBG", 0);
-  a.dbg = slab_dbg;
   a.kd1 = kd1;
   if (bp == 128) {  // [SLAB-BD] 128-position bands (4x4 maps: 8 padded samples = 288 union rows)
     const int nCO = Cout / 128;
     const dim3 grid((unsigned)((int64_t)a.nPB * nCO * G));
-    hipLaunchKernelGGL((k_conv_fwd_slab<128, 2, 2, 384, true, false, false, false>), grid, dim3(256), 0,
+    hipLaunchKernelGGL((k_conv_fwd_slab<128, 2, 2, 384, true, false, false>), grid, dim3(256), 0,
                        as_stream(stream), a, nCO, ptr<const int>(utab));
     NIDT_CHECK(hipGetLastError());
     return;
@@ -1617,39 +1402,14 @@ static void fwd_slab_impl(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias
   const dim3 grid((unsigned)((int64_t)a.nPB * nCO * G));
   hipStream_t s = as_stream(stream);
   const int* tab = ptr<const int>(utab);
-  // NIDT_SLAB_LSWZ=1: output-space swizzle (A/B: no gain measured, see [LSWZ])
-  static const int lswz = env_int("NIDT_SLAB_LSWZ", 0);
-  // NIDT_SLAB_NA=3: three weight-tile stages for the 64-channel blocks (A/B)
-  static const bool na3 = env_int("NIDT_SLAB_NA", 0) == 3;
-  // [SCHED] fragment schedule for the 64-channel blocks (AlexNet conv2 data gradient 3.25 -> 3.00 ms at 64 clients,
-  // profiles/r4_ab_slab_sched.txt; the 128-channel blocks would need > 128 VGPRs and lose their second block per CU:
-  // conv2 forward 2.55 -> 3.23 ms).  NIDT_SLAB_SCHED=0: the compiler's schedule (A/B); =2 adds [SCHED-half] on the
-  // 128-channel blocks (A/B)
-  static const int sched = env_int("NIDT_SLAB_SCHED", 1);
-  // (8-wave 64-channel blocks, two 32-channel halves: conv2 data gradient 3.49 vs 3.25 ms — more VALU per MFMA from
-  // the duplicated B addressing; profiles/r4_ab_slab_sched.txt, not kept)
-  // the switches above as one kernel variant, first match wins: (LSW, NA, SCHED) template arguments
-  enum { kPlain, kLswz, kNa3, kSched, kSchedHalf };
-  const int variant = lswz ? kLswz
-                      : (na3 && bco == 64) ? kNa3
-                      : (sched && bco == 64) ? kSched
-                      : (sched == 2 && bco == 128 && !pad) ? kSchedHalf
-                      : kPlain;
   dispatch_int<128, 64>(bco, [&](auto bc) {
     dispatch_int<384, 416>(bco == 128 ? 384 : slab_u(B, D, H, W, pad), [&](auto uu) {
       dispatch_bool(pad != 0, [&](auto pd) {
         dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
-          dispatch_int<kPlain, kLswz, kNa3, kSched, kSchedHalf>(variant, [&](auto v) {
-            constexpr int BC = bc.value, WM = BC / 64, V = v.value;
-            constexpr bool PD = pd.value;
-            // 416-row unions, three weight stages and [SCHED] exist for the 64-channel blocks only, [SCHED-half] for
-            // the unpadded 128-channel blocks only
-            if constexpr ((BC == 64 || uu.value == 384) && (BC == 64 || (V != kNa3 && V != kSched)) &&
-                          (V != kSchedHalf || (BC == 128 && !PD)))
-              hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, uu.value, PD, bi.value, sts.value, V == kLswz,
-                                                  V == kNa3 ? 3 : 2, V == kSched ? 1 : (V == kSchedHalf ? 2 : 0)>),
-                                 grid, dim3(256 * WM), 0, s, a, nCO, tab);
-          });
+          constexpr int BC = bc.value, WM = BC / 64;
+          if constexpr (BC == 64 || uu.value == 384)  // 416-row unions exist for the 64-channel blocks only
+            hipLaunchKernelGGL((k_conv_fwd_slab<BC, WM, 4, uu.value, pd.value, bi.value, sts.value>), grid,
+                               dim3(256 * WM), 0, s, a, nCO, tab);
         });
       });
     });
@@ -1757,50 +1517,6 @@ void conv2d_fwd_slab_bd(uintptr_t x, uintptr_t w, uintptr_t y, int G, int B, int
   const int bp = slab_bd_bp(B, H, W, Cin, Cout);
   NIDT_REQUIRE(bp > 0, "conv2d_fwd_slab_bd: shape not supported");
   fwd_slab_impl(x, w, 0, 0, y, 0, G, 1, B, H, W, Cin, Cout, 1, 9, utab, stream, 1, bp);
-}
-
-// ---- k_conv_fwd_vol host side (whole padded sample <= 448 rows, <= 256 output positions per sample) ----
-constexpr int kVolU = 448;
-int conv3d_fwd_vol_ok(int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  if (Cin % 64 != 0 || Cout % 64 != 0 || pad < 0 || pad > 2 || Cin > kMaxCin || B < 1) return 0;
-  const int Do = D + 2 * pad - 2, Ho = H + 2 * pad - 2, Wo = W + 2 * pad - 2;
-  if (Do < 1 || Ho < 1 || Wo < 1 || Do * Ho * Wo > 256) return 0;
-  return (D + 2 * pad) * (H + 2 * pad) * (W + 2 * pad) <= kVolU ? 1 : 0;
-}
-
-// Opt-in (NIDT_FWD_VOL=1): measured slower than the per-tap kernel for the 5x7x5 conv3-5 at 64 clients (fwd + dgrad
-// 2.19 vs 1.71 ms per step: 3-wave blocks, one exposed weight-tile wait per tap) and within 1 % at 8 clients
-// (profiles/r3_ab_fwd_vol.txt).  When enabled: grids of >= NIDT_FWD_VOL_MINB (256) blocks without split-K.
-int conv3d_fwd_vol_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = env_int("NIDT_FWD_VOL", 0);
-  static const int minb = env_int("NIDT_FWD_VOL_MINB", 256);
-  if (!env || !conv3d_fwd_vol_ok(B, D, H, W, Cin, Cout, pad)) return 0;
-  const int Mg = out_positions(B, D, H, W, pad);
-  if (conv3d_fwd_ksplit(Cin, Cout, G, Mg) > 1) return 0;
-  return (int64_t)G * B * (Cout / 64) >= minb ? 1 : 0;
-}
-
-void conv3d_fwd_vol(uintptr_t x, uintptr_t w, uintptr_t bias, int64_t bias_ld, uintptr_t y, uintptr_t stats, int G,
-                    int B, int D, int H, int W, int Cin, int Cout, int pad, uintptr_t stream) {
-  NIDT_REQUIRE(conv3d_fwd_vol_ok(B, D, H, W, Cin, Cout, pad), "conv3d_fwd_vol: shape not supported");
-  NIDT_REQUIRE((int64_t)B * D * H * W * Cin * 2 < (1ll << 31), "conv3d_fwd_vol: per-client input below 2 GiB");
-  const bool hb = bias != 0, st = stats != 0;
-  NIDT_REQUIRE(!st || hb, "conv3d_fwd_vol: statistics require a bias");
-  ConvFwdArgs a = fwd_args_s1k3(x, w, bias, bias_ld, y, stats, G, B, D, H, W, Cin, Cout, pad, 27, 256);
-  a.nPB = B;  // statistics blocks = samples
-  const int S = a.Do * a.Ho * a.Wo, nCO = Cout / 64;
-  static const int wm = env_int("NIDT_FWD_VOL_WM", 1);
-  const dim3 grid((unsigned)((int64_t)G * B * nCO));
-  hipStream_t s = as_stream(stream);
-  dispatch_int<1, 2>(wm == 2 ? 2 : 1, [&](auto wmc) {
-    dispatch_int<1, 2, 3, 4>(ceil_div(S, 64), [&](auto wn) {  // S <= 256 positions per sample
-      dispatch_epilogue(hb, st, [&](auto bi, auto sts) {
-        hipLaunchKernelGGL((k_conv_fwd_vol<64, wmc.value, wn.value, kVolU, bi.value, sts.value>), grid,
-                           dim3(64 * wmc.value * wn.value), 0, s, a, nCO);
-      });
-    });
-  });
-  NIDT_CHECK(hipGetLastError());
 }
 
 int conv3d_fwd_nblocks(int B, int D, int H, int W, int pad, int bp) {
@@ -2007,8 +1723,8 @@ static bool wg1x1_on(int Cin, int Cout, int kt, int st) {
 // waves x block time with waves = ceil(blocks / slots), slots = 256 CUs x 2 resident blocks (80 KB LDS each),
 // plus the fp32 slab traffic (ns x G x Cout x K, written once and read once by k_wgrad_reduce).  The model
 // (one 64-position step ~1.28 us per block slot, ~12 steps of prologue/epilogue, ~5 TB/s slab traffic) picks the
-// ns with the smallest estimate; ties go to the smaller ns.  NIDT_WG_NSPLIT_LEGACY=1 restores the old rule
-// (ceil(2048 / tiles), capped) for A/B measurements.
+// ns with the smallest estimate; ties go to the smaller ns (tried, lost: ceil(2048 / tiles), capped,
+// profiles/r1_ab_wgrad_nsplit.txt).
 static int wgrad_nsplit_mk(int G, int Mg, int K, int Cout);
 
 int conv3d_wgrad_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
@@ -2033,15 +1749,6 @@ static int wgrad_nsplit_mk(int G, int Mg, int K, int Cout) {
 // 64-position step per block slot and its fixed cost in steps
 static int wgrad_nsplit_base(int base, int G, int Mg, int K, int Cout, double step_us, double overhead_steps,
                              double slots) {
-  static const bool legacy = env_int("NIDT_WG_NSPLIT_LEGACY", 0) == 1;
-  // A/B experiments only: one split factor for every layer
-  static const int force = env_int("NIDT_WG_NSPLIT_FORCE", 0);
-  if (force > 0) return std::max(1, std::min(force, std::max(1, Mg / 64)));
-  if (legacy) {
-    const int ns = ceil_div(2048, base);
-    const int maxns = max(1, Mg / (K >= 3000 ? 1024 : 512));
-    return max(1, min(ns, maxns));
-  }
   constexpr double kBytesPerUs = 5.0e6;
   const double kSlots = slots;  // resident blocks chip-wide
   const double kStepUs = step_us, kOverheadSteps = overhead_steps;
@@ -2106,24 +1813,25 @@ constexpr int kWdGroup = kWdPos * kWdRow;        // one 64-col group: 8 KB
 constexpr int kWdBuf = 5 * kWdGroup;             // 4 X groups + dY
 __device__ __forceinline__ int swz_wd(int r) { return (r & 2) | ((r >> 1) & 4); }
 
-// NCH = 64-channel output halves per block: 1 -> 4 waves (64 co x 256 k-cols), 2 -> 8 waves (128 co x 256 k-cols:
-// the X tile of a k-step feeds twice the MFMAs, 48 KB of LDS-DMA per 256 MFMAs instead of 40 KB per 128).
-// Wave (wc, wk) = (wid / 4, wid % 4) computes co half wc x X group wk; it stages 8/NCH of group wk's 8 X
-// instructions and dY half wc's slices 2wk, 2wk+1.
+// Wave wk = wid computes the block's 64 co x X group wk; it stages group wk's 8 X instructions and dY slices 2wk,
+// 2wk+1.  The k-step runs under [SCHED] (kstep_sched: AlexNet conv3-5 weight gradients at 8 clients -2.7 %, config 5
+// 12.16 -> 12.10 s/round, profiles/r4_ab_sched_more.txt).
 // [ADMA] as k_conv_wgrad_tri: the stage DMA from inline asm, the position-table loads issued before it
-template <int NCH, bool SCHED = false, bool ADMA = false>
-__global__ __launch_bounds__(256 * NCH, 2 / NCH) void k_conv_wgrad_dma(ConvWgDmaArgs a) {
-  constexpr int BUFE = (4 + NCH) * kWdGroup;  // elements per stage: 4 X groups + NCH dY halves
-  constexpr int XI = 8 / NCH;                  // X instructions per wave per stage
+// Tried, lost: 128-channel blocks (8 waves, the X tile feeds both halves: conv2 wgrad 3.91 -> 4.14 ms at 64 clients,
+// 0.505 -> 0.542 ms at 8, profiles/r2_ab_wgrad_nch.txt — the kernel is latency/barrier bound, not L2->LDS bandwidth
+// bound); the compiler's schedule and the intrinsic DMA (profiles/r4_ab_sched_more.txt, r6_wgrad_adma.txt)
+__global__ __launch_bounds__(256, 2) void k_conv_wgrad_dma(ConvWgDmaArgs a) {
+  constexpr int BUFE = kWdBuf;  // elements per stage: 4 X groups + dY
+  constexpr int XI = 8;         // X instructions per wave per stage
   __shared__ __attribute__((aligned(16))) uint16_t smem[2 * BUFE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform: LDS destinations stay in SGPRs
-  const int wc = wid >> 2, wk = wid & 3;
+  const int wc = wid >> 2, wk = wid & 3;  // wc = 0: the block's four waves are the X groups
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int kt = id % a.nKT, r1 = id / a.nKT;
   const int ct = r1 % a.nCT, r2 = r1 / a.nCT;
   const int sp = r2 % a.nsplit, g = r2 / a.nsplit;
-  const int kc0 = kt * kWgKC, co0 = ct * (kWgCO * NCH);
+  const int kc0 = kt * kWgKC, co0 = ct * kWgCO;
   const int p_begin = sp * a.chunk, p_end = min(a.Mg, p_begin + a.chunk);
   const int Cin = a.Cin;
   const i32x4_t rx = make_rsrc(a.x + (int64_t)g * a.xclient, (uint32_t)(a.xclient * 2));
@@ -2151,20 +1859,16 @@ __global__ __launch_bounds__(256 * NCH, 2 / NCH) void k_conv_wgrad_dma(ConvWgDma
     _Pragma("unroll") for (int i_ = 0; i_ < XI; ++i_)                                                         \
       tn[i_] = nidt_raw_buffer_load_v2i32(rt, ((P0) + 8 * (xi0 + i_) + lr) * 8, 0, 0);                        \
   }
-  auto wd_dma = [](i32x4_t r, int off, uint16_t* dst) {
-    if constexpr (ADMA) blds16_asm(r, off, dst);
-    else blds16(r, off, dst);
-  };
 #define WD_ISSUE_T(P0, BUFI, TN)                                                                              \
   {                                                                                                           \
     uint16_t* sX_ = smem + (BUFI) * BUFE + wk * kWdGroup;                                                     \
     uint16_t* sD_ = smem + (BUFI) * BUFE + (4 + wc) * kWdGroup;                                               \
     _Pragma("unroll") for (int i_ = 0; i_ < XI; ++i_) {                                                       \
       const bool ok_ = (TN[i_].y >> gtap) & 1;                                                                \
-      wd_dma(rx, ok_ ? TN[i_].x * (2 * Cin) + xcol[i_] : kBufOOB, sX_ + (xi0 + i_) * 512);                    \
+      blds16_asm(rx, ok_ ? TN[i_].x * (2 * Cin) + xcol[i_] : kBufOOB, sX_ + (xi0 + i_) * 512);                \
     }                                                                                                         \
     _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                          \
-      wd_dma(rd, (P0) * (2 * a.Cout) + dcol[i_], sD_ + (2 * wk + i_) * 512);                                  \
+      blds16_asm(rd, (P0) * (2 * a.Cout) + dcol[i_], sD_ + (2 * wk + i_) * 512);                              \
   }
 #define WD_ISSUE(P0, BUFI) WD_ISSUE_T(P0, BUFI, tn)
 
@@ -2188,55 +1892,23 @@ __global__ __launch_bounds__(256 * NCH, 2 / NCH) void k_conv_wgrad_dma(ConvWgDma
   }
   for (int st = 0; st < nsteps; ++st) {
     const int cur = st & 1;
-    if constexpr (ADMA) {
-      i32x2_t tdma[XI];  // the table entries of step st + 1, fetched a step ago
+    i32x2_t tdma[XI];  // the table entries of step st + 1, fetched a step ago
 #pragma unroll
-      for (int i = 0; i < XI; ++i) tdma[i] = tn[i];
-      if (st + 1 < nsteps) {
-        if (st + 2 < nsteps) WD_FETCH(p_begin + kWdPos * (st + 2))
-        WD_ISSUE_T(p_begin + kWdPos * (st + 1), cur ^ 1, tdma)
-      }
-    } else if (st + 1 < nsteps) {
-      WD_ISSUE(p_begin + kWdPos * (st + 1), cur ^ 1)
+    for (int i = 0; i < XI; ++i) tdma[i] = tn[i];
+    if (st + 1 < nsteps) {
       if (st + 2 < nsteps) WD_FETCH(p_begin + kWdPos * (st + 2))
+      WD_ISSUE_T(p_begin + kWdPos * (st + 1), cur ^ 1, tdma)
     }
     const uint16_t* sX = smem + cur * BUFE + wk * kWdGroup;
     const uint16_t* sD = smem + cur * BUFE + (4 + wc) * kWdGroup;
-    if constexpr (SCHED) {  // [SCHED] (kstep_sched)
-      auto frag = [&](const uint16_t* base, int kk, int i) {
-        const int ra = 32 * kk + rr0, rb = 32 * kk + rr1, c = 2 * i + (pp >> 1);
-        return tr_pair(base + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
-                       base + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
-      };
-      kstep_sched<4, 4, 2>(acc, [&](int kk, int i) { return frag(sD, kk, i); },
-                           [&](int kk, int j) { return frag(sX, kk, j); });
-    } else {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {  // two 32-position MFMA k-steps
-      const int ra = 32 * kk + rr0, rb = 32 * kk + rr1;
-      bf16x8 fa[4], fb[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int c = 2 * i + (pp >> 1);
-        fa[i] = tr_pair(sD + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
-                        sD + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
-        fb[i] = tr_pair(sX + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
-                        sX + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    }
-    }
-    if constexpr (ADMA) {
-      __builtin_amdgcn_s_waitcnt(7 << 4);  // vmcnt(0) lgkmcnt(0), visible to the waitcnt pass (k_conv_wgrad_tri)
-    } else {
-      // retire this step's LDS-DMA (next stage) but leave the XI position-table loads for step st+2 in flight: they
-      // are the youngest vector-memory ops and are only consumed by the next step's DMA issue
-      if (st + 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XI) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    auto frag = [&](const uint16_t* base, int kk, int i) {
+      const int ra = 32 * kk + rr0, rb = 32 * kk + rr1, c = 2 * i + (pp >> 1);
+      return tr_pair(base + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
+                     base + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
+    };
+    kstep_sched<4, 4, 2>(acc, [&](int kk, int i) { return frag(sD, kk, i); },
+                         [&](int kk, int j) { return frag(sX, kk, j); });
+    __builtin_amdgcn_s_waitcnt(7 << 4);  // vmcnt(0) lgkmcnt(0), visible to the waitcnt pass (k_conv_wgrad_tri)
     __syncthreads();
   }
 #undef WD_ISSUE
@@ -2281,10 +1953,9 @@ __global__ __launch_bounds__(256 * NCH, 2 / NCH) void k_conv_wgrad_dma(ConvWgDma
 // busy with its waves parked on the DMA 55 % of the time (profiles/r2_pmc_alexnet_g64.txt).  The taps kw = 0,1,2
 // of one (kd, kh) read padded-input rows b(p) + kw: for 64 consecutive output positions the union of those rows
 // is a few runs of consecutive padded rows (74 for conv2, 92 for the padded 5x7x5 conv3-5; one run per band of
-// output rows, split where the band crosses a depth slice or a sample).  A block owns 64 NCH output channels x
+// output rows, split where the band crosses a depth slice or a sample).  A block owns 64 output channels x
 // one (kd, kh, 64-channel chunk) triplet = 192 k-columns; per k-step it stages the union (<= U rows) and the dY
-// tile: conv2 (NCH 2) 26 KB per 192 MFMAs, 2.3x fewer bytes per MFMA.  Wave (wc, kw) computes co block wc x tap
-// kw; its X fragment rows are union row idx(p) + kw.  Step table (k_union_table, per 64-position step of a
+// tile.  Wave kw computes tap kw; its X fragment rows are union row idx(p) + kw.  Step table (k_union_table, per 64-position step of a
 // client): per union row {voxel offset of its (kd, kh) = (0, 0) source, padded (d, h, w) code} and idx(p); a
 // row whose source for this block's (kd, kh) lies in the padding reads out of range -> 0.
 template <int U>
@@ -2377,27 +2048,27 @@ static int wgrad_tri_umax(int B, int D, int H, int W, int pad) { return union_um
 // largest union (rows) of a P-position band: exposed for host-side tests of the union rule
 int conv3d_union_umax(int B, int D, int H, int W, int pad, int P) { return union_umax(B, D, H, W, pad, P); }
 
-// [LSW] as k_conv_fwd_slab: the X union rows' chunk swizzle is keyed by their output-space index L = (d Ho + h) Wo + w
-// (the positions of one ds_read_b64_tr_b16 read L = p + kw for 8 positions p, consecutive within the step except at
-// the 32-position kk halves, where the union rows jump at output-row ends; modelled for conv2: 1.52 LDS cycles per X
-// read -> 1.00).  The dY rows are the step's positions themselves and keep swz_wd of their row.  Measured: conflicts
-// 20.8 / 33.2 % -> 0.1 / 1.7 % (conv2 / conv3-5) but conv2 2.92-2.98 -> 3.22-3.29 ms (the per-step swizzle of the
-// DMA addresses sits on the issue path); opt-in NIDT_WGTRI_LSWZ=1 (profiles/r4_ab_lds_swizzle.txt).
+// The k-step runs under [SCHED] (kstep_sched: AlexNet conv2-5 weight gradients at 64 clients 4.28 -> 4.24 ms,
+// profiles/r4_ab_sched_more.txt).
+// Tried, lost: 128-channel blocks (6 waves: slower on every AlexNet layer, conv2 3.28 vs 3.06 ms at 64 clients,
+// profiles/r2_ab_wgrad_tri.txt); an X chunk swizzle keyed by the rows' output-space index (conflicts 20.8 / 33.2 % ->
+// 0.1 / 1.7 % but conv2 2.92-2.98 -> 3.22-3.29 ms: the per-step swizzle of the DMA addresses sits on the issue path,
+// profiles/r4_ab_lds_swizzle.txt)
 // [ADMA] the stage DMA issued from inline asm (blds16_asm) instead of the intrinsic: the compiler's waitcnt pass
 // treats an intrinsic LDS-DMA as a write to LDS that the fragment reads of the current stage may alias, and put a
 // vmcnt wait for the next stage's DMA (issued at the top of the step) in front of them — the double buffer never
 // overlapped a transfer with the MFMAs of its own wave.  The kernel's counted waits at the end of each step already
 // order every DMA before its stage is read; M0 is used by nothing else here.
-template <int NCH, int U, bool PADDED, bool LSW = true, bool SCHED = false, bool ADMA = false>
-__global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a) {
-  constexpr int NW = 3 * NCH, XG = U * kWdRow, BUFE = XG + NCH * kWdGroup, ST = WtTab<U>::kST;
+template <int U, bool PADDED>
+__global__ __launch_bounds__(192, 2) void k_conv_wgrad_tri(ConvWgTriArgs a) {
+  constexpr int NW = 3, XG = U * kWdRow, BUFE = XG + kWdGroup, ST = WtTab<U>::kST;
   constexpr int XP = U / 8, XPW = (XP + NW - 1) / NW;       // union pieces (8 rows each) per wave
-  constexpr int DP = 8 * NCH, DPW = (DP + NW - 1) / NW;     // dY pieces (8 positions x 64 co) per wave
+  constexpr int DP = 8, DPW = (DP + NW - 1) / NW;           // dY pieces (8 positions x 64 co) per wave
   __shared__ __attribute__((aligned(16))) uint16_t smem[2 * BUFE];
   auto stage = [&](int k) -> uint16_t* { return smem + k * BUFE; };
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wc = wid / 3, kw = wid - 3 * wc;
+  const int wc = wid / 3, kw = wid - 3 * wc;  // wc = 0: the block's three waves are the kw taps
   const int id = xcd_remap(blockIdx.x, gridDim.x);
   const int kt = id % a.nKT, r1 = id / a.nKT;
   const int ct = r1 % a.nCT, r2 = r1 / a.nCT;
@@ -2405,7 +2076,7 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
   const int Cin = a.Cin, nck = Cin / 64;
   const int trip = kt / nck, cc = kt - trip * nck;  // trip = kd * 3 + kh
   const int kd = trip / 3, kh = trip - 3 * kd;
-  const int co0 = ct * 64 * NCH;
+  const int co0 = ct * 64;
   const int p_begin = sp * a.chunk, p_end = min(a.Mg, p_begin + a.chunk);
   const i32x4_t rx = make_rsrc(a.x + (int64_t)g * a.xclient, (uint32_t)(a.xclient * 2));
   const i32x4_t rd = make_rsrc(a.dy + (int64_t)g * a.Mg * a.Cout, (uint32_t)((int64_t)a.Mg * a.Cout * 2));
@@ -2417,9 +2088,8 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
 #pragma unroll
   for (int i = 0; i < XPW; ++i) {
     const int u = 8 * (wid * XPW + i) + lr;
-    xcol[i] = (cc * 64 + (LSW ? 0 : ((ls ^ swz_wd(u)) << 3))) * 2;
+    xcol[i] = (cc * 64 + ((ls ^ swz_wd(u)) << 3)) * 2;
   }
-  const int Ho = a.H + 2 * a.pad - 2, Wo = a.W + 2 * a.pad - 2, So = (a.D + 2 * a.pad - 2) * Ho * Wo;
 #pragma unroll
   for (int i = 0; i < DPW; ++i) {
     const int dp = min(wid * DPW + i, DP - 1), h = dp >> 3, sl = dp & 7, r = 8 * sl + lr;
@@ -2430,10 +2100,6 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
   const int rr0 = 8 * gq + qq, rr1 = rr0 + 4;
   i32x2_t trow[XPW];
   int tix[4], tixn[4];
-  auto wt_dma = [](i32x4_t r, int off, uint16_t* dst) {
-    if constexpr (ADMA) blds16_asm(r, off, dst);
-    else blds16(r, off, dst);
-  };
 #define WT_FETCH_ROWS(S)                                                                                      \
   {                                                                                                           \
     _Pragma("unroll") for (int i_ = 0; i_ < XPW; ++i_)                                                        \
@@ -2456,11 +2122,10 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
                                    (unsigned)(((c_ >> 10) & 1023) - hlo) < (unsigned)a.H &&                   \
                                    (unsigned)((c_ >> 20) - a.pad) < (unsigned)a.W)                            \
                                 : (c_ & 1023) != 1023;                                                        \
-        const int sw_ = LSW ? ((ls ^ swz_wd(((c_ & 1023) * Ho + ((c_ >> 10) & 1023)) * Wo + (c_ >> 20))) << 4) : 0; \
-        wt_dma(rx, ok_ ? (TR[i_].x + xadd) * (2 * Cin) + xcol[i_] + sw_ : kBufOOB, sX_ + (wid * XPW + i_) * 512); \
+        blds16_asm(rx, ok_ ? (TR[i_].x + xadd) * (2 * Cin) + xcol[i_] : kBufOOB, sX_ + (wid * XPW + i_) * 512);  \
       }                                                                                                       \
     _Pragma("unroll") for (int i_ = 0; i_ < DPW; ++i_)                                                        \
-      if (wid * DPW + i_ < DP) wt_dma(rd, (S) * 64 * (2 * a.Cout) + dcol[i_], sD_ + dls[i_]);               \
+      if (wid * DPW + i_ < DP) blds16_asm(rd, (S) * 64 * (2 * a.Cout) + dcol[i_], sD_ + dls[i_]);           \
   }
 #define WT_ISSUE(S, BUFI) WT_ISSUE_R(S, BUFI, trow)
 
@@ -2471,53 +2136,21 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int s0 = p_begin / 64, nsteps = (p_end - p_begin + 63) / 64;
-  // output-space index (within the sample) of the four fragment positions of this lane, advanced by 64 per step
-  int lpos[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) lpos[k] = (s0 * 64 + 32 * (k >> 1) + ((k & 1) ? rr1 : rr0)) % So;
   // the k-step: 32 MFMAs per wave from stage buffer `buf` with union-row indices tx of this step's positions
   auto compute = [&](const uint16_t* sX, const int (&tx)[4]) {
     const uint16_t* sD = sX + XG + wc * kWdGroup;
-    if constexpr (SCHED) {  // [SCHED] (kstep_sched)
-      kstep_sched<4, 4, 2>(
-          acc,
-          [&](int kk, int i) {
-            const int ra = 32 * kk + rr0, rb = 32 * kk + rr1, c = 2 * i + (pp >> 1);
-            return tr_pair(sD + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
-                           sD + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
-          },
-          [&](int kk, int j) {
-            const int xa = tx[2 * kk] + kw, xb = tx[2 * kk + 1] + kw, c = 2 * j + (pp >> 1);
-            const int sxa = swz_wd(LSW ? lpos[2 * kk] + kw : xa), sxb = swz_wd(LSW ? lpos[2 * kk + 1] + kw : xb);
-            return tr_pair(sX + xa * kWdRow + ((c ^ sxa) << 3) + (pp & 1) * 4,
-                           sX + xb * kWdRow + ((c ^ sxb) << 3) + (pp & 1) * 4);
-          });
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ra = 32 * kk + rr0, rb = 32 * kk + rr1;
-        const int xa = tx[2 * kk] + kw, xb = tx[2 * kk + 1] + kw;
-        const int sxa = swz_wd(LSW ? lpos[2 * kk] + kw : xa), sxb = swz_wd(LSW ? lpos[2 * kk + 1] + kw : xb);
-        bf16x8 fa[4], fb[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int c = 2 * i + (pp >> 1);
-          fa[i] = tr_pair(sD + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
-                          sD + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
-          fb[i] = tr_pair(sX + xa * kWdRow + ((c ^ sxa) << 3) + (pp & 1) * 4,
-                          sX + xb * kWdRow + ((c ^ sxb) << 3) + (pp & 1) * 4);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      lpos[k] += 64;
-      lpos[k] -= lpos[k] >= So ? So : 0;  // So >= 64 for every eligible shape (host check)
-    }
+    kstep_sched<4, 4, 2>(  // [SCHED]
+        acc,
+        [&](int kk, int i) {
+          const int ra = 32 * kk + rr0, rb = 32 * kk + rr1, c = 2 * i + (pp >> 1);
+          return tr_pair(sD + ra * kWdRow + ((c ^ swz_wd(ra)) << 3) + (pp & 1) * 4,
+                         sD + rb * kWdRow + ((c ^ swz_wd(rb)) << 3) + (pp & 1) * 4);
+        },
+        [&](int kk, int j) {
+          const int xa = tx[2 * kk] + kw, xb = tx[2 * kk + 1] + kw, c = 2 * j + (pp >> 1);
+          return tr_pair(sX + xa * kWdRow + ((c ^ swz_wd(xa)) << 3) + (pp & 1) * 4,
+                         sX + xb * kWdRow + ((c ^ swz_wd(xb)) << 3) + (pp & 1) * 4);
+        });
   };
   if (nsteps > 0) {
     WT_FETCH_ROWS(s0)
@@ -2532,35 +2165,22 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
     const int cur = st & 1;
 #pragma unroll
     for (int k = 0; k < 4; ++k) tix[k] = tixn[k];
-    if constexpr (ADMA) {
-      // [ADMA] the step-table loads (rows of st + 2, indices of st + 1) go out first, then the asm DMA of st + 1 from
-      // the rows fetched a step ago (rdma): the compiler, which counts only the loads it sees, never has to wait for
-      // anything younger than the DMA to feed it, and nothing of this step reads those new registers, so the only
-      // wait for the DMA is ours at the end of the step — the transfer overlaps this step's MFMAs
-      i32x2_t rdma[XPW];
+    // [ADMA] the step-table loads (rows of st + 2, indices of st + 1) go out first, then the asm DMA of st + 1 from
+    // the rows fetched a step ago (rdma): the compiler, which counts only the loads it sees, never has to wait for
+    // anything younger than the DMA to feed it, and nothing of this step reads those new registers, so the only
+    // wait for the DMA is ours at the end of the step — the transfer overlaps this step's MFMAs
+    i32x2_t rdma[XPW];
 #pragma unroll
-      for (int i = 0; i < XPW; ++i) rdma[i] = trow[i];
-      if (st + 1 < nsteps) {
-        if (st + 2 < nsteps) WT_FETCH_ROWS(s0 + st + 2)
-        WT_FETCH_IDX(s0 + st + 1, tixn)
-        WT_ISSUE_R(s0 + st + 1, cur ^ 1, rdma)
-      }
-      compute(stage(cur), tix);
-      // s_waitcnt vmcnt(0) lgkmcnt(0) as the builtin, which the waitcnt pass sees (with an asm wait it would still
-      // count this step's table loads as pending and wait for them in front of the next step's DMA)
-      __builtin_amdgcn_s_waitcnt(7 << 4);
-    } else {
-      if (st + 1 < nsteps) {
-        WT_ISSUE(s0 + st + 1, cur ^ 1)
-        if (st + 2 < nsteps) WT_FETCH_ROWS(s0 + st + 2)
-        WT_FETCH_IDX(s0 + st + 1, tixn)
-      }
-      compute(stage(cur), tix);
-      // retire the next stage's LDS-DMA; the step-table loads issued after it (rows for st+2, idx for st+1) may stay
-      if (st + 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XPW + 4) : "memory");
-      else if (st + 1 < nsteps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    for (int i = 0; i < XPW; ++i) rdma[i] = trow[i];
+    if (st + 1 < nsteps) {
+      if (st + 2 < nsteps) WT_FETCH_ROWS(s0 + st + 2)
+      WT_FETCH_IDX(s0 + st + 1, tixn)
+      WT_ISSUE_R(s0 + st + 1, cur ^ 1, rdma)
     }
+    compute(stage(cur), tix);
+    // s_waitcnt vmcnt(0) lgkmcnt(0) as the builtin, which the waitcnt pass sees (with an asm wait it would still
+    // count this step's table loads as pending and wait for them in front of the next step's DMA)
+    __builtin_amdgcn_s_waitcnt(7 << 4);
     __syncthreads();
   }
 #undef WT_ISSUE
@@ -2587,8 +2207,10 @@ __global__ __launch_bounds__(192 * NCH, 2) void k_conv_wgrad_tri(ConvWgTriArgs a
 // 96 per 18 KB (k_conv_wgrad_tri, which the PMC shows waiting on those transfers).  Wave (kh, j) = (wid / 4,
 // wid % 4) owns ci tile j of taps (kh, 0..2) for all four co tiles: X row of tap (kh, kw) = idx(p) + kh Wp + kw.
 // Output: fp32 slabs per split (k_wgrad_reduce finishes), as k_conv_wgrad_tri.
+// No launcher picks it (measured slower at 64 clients: conv2 3.83 vs 3.03 ms, conv3-5 0.44-0.63 vs 0.36-0.53 ms,
+// profiles/r3_ab_wgrad_slab.txt): it is reached through conv3d_wgrad_slab only.
 // [ADMA] as k_conv_wgrad_tri: the stage DMA from inline asm, the step-table loads issued before it, the builtin wait
-template <int U, bool PADDED, bool ADMA = false>
+template <int U, bool PADDED>
 __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
   constexpr int NW = 12, XG = U * kWdRow, BUFE = XG + kWdGroup, ST = WtTab<U>::kST;
   constexpr int XP = U / 8, XPW = (XP + NW - 1) / NW;   // union pieces (8 rows each) per wave
@@ -2634,10 +2256,6 @@ __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
       DST[k_] = nidt_raw_buffer_load_i32(rt, ((S) * ST + 2 * U + 32 * (k_ >> 1) + ((k_ & 1) ? rr1 : rr0)) * 4, \
                                          0, 0);                                                               \
   }
-  auto ws_dma = [](i32x4_t r, int off, uint16_t* dst) {
-    if constexpr (ADMA) blds16_asm(r, off, dst);
-    else blds16(r, off, dst);
-  };
 #define WS_ISSUE_R(S, BUFI, TR)                                                                               \
   {                                                                                                           \
     uint16_t* sX_ = smem + (BUFI) * BUFE;                                                                     \
@@ -2648,9 +2266,9 @@ __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
                                    (unsigned)(((c_ >> 10) & 1023) - a.pad) < (unsigned)a.H &&                 \
                                    (unsigned)((c_ >> 20) - a.pad) < (unsigned)a.W)                            \
                                 : (c_ & 1023) != 1023;                                                        \
-        ws_dma(rx, ok_ ? (TR[i_].x + xadd) * (2 * Cin) + xcol[i_] : kBufOOB, sX_ + (wid * XPW + i_) * 512);    \
+        blds16_asm(rx, ok_ ? (TR[i_].x + xadd) * (2 * Cin) + xcol[i_] : kBufOOB, sX_ + (wid * XPW + i_) * 512); \
       }                                                                                                       \
-    if (dload) ws_dma(rd, (S) * 64 * (2 * a.Cout) + dcol, sX_ + XG + (wid & 7) * 512);                       \
+    if (dload) blds16_asm(rd, (S) * 64 * (2 * a.Cout) + dcol, sX_ + XG + (wid & 7) * 512);                   \
   }
 #define WS_ISSUE(S, BUFI) WS_ISSUE_R(S, BUFI, trow)
 
@@ -2675,19 +2293,13 @@ __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
     const int cur = st & 1;
 #pragma unroll
     for (int k = 0; k < 4; ++k) tix[k] = tixn[k];
-    if constexpr (ADMA) {
-      i32x2_t rdma[XPW];
+    i32x2_t rdma[XPW];
 #pragma unroll
-      for (int i = 0; i < XPW; ++i) rdma[i] = trow[i];
-      if (st + 1 < nsteps) {
-        if (st + 2 < nsteps) WS_FETCH_ROWS(s0 + st + 2)
-        WS_FETCH_IDX(s0 + st + 1, tixn)
-        WS_ISSUE_R(s0 + st + 1, cur ^ 1, rdma)
-      }
-    } else if (st + 1 < nsteps) {
-      WS_ISSUE(s0 + st + 1, cur ^ 1)
+    for (int i = 0; i < XPW; ++i) rdma[i] = trow[i];
+    if (st + 1 < nsteps) {
       if (st + 2 < nsteps) WS_FETCH_ROWS(s0 + st + 2)
       WS_FETCH_IDX(s0 + st + 1, tixn)
+      WS_ISSUE_R(s0 + st + 1, cur ^ 1, rdma)
     }
     const uint16_t* sX = smem + cur * BUFE;
     const uint16_t* sD = sX + XG;
@@ -2713,14 +2325,7 @@ __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[kw][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[kw], acc[kw][i], 0, 0, 0);
     }
-    if constexpr (ADMA) {
-      __builtin_amdgcn_s_waitcnt(7 << 4);  // vmcnt(0) lgkmcnt(0), visible to the waitcnt pass (k_conv_wgrad_tri)
-    } else {
-      // retire the next stage's LDS-DMA; the step-table loads issued after it (rows for st+2, idx for st+1) may stay
-      if (st + 2 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XPW + 4) : "memory");
-      else if (st + 1 < nsteps) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    __builtin_amdgcn_s_waitcnt(7 << 4);  // vmcnt(0) lgkmcnt(0), visible to the waitcnt pass (k_conv_wgrad_tri)
     __syncthreads();
   }
 #undef WS_ISSUE
@@ -2739,27 +2344,15 @@ __global__ __launch_bounds__(768, 1) void k_conv_wgrad_slab(ConvWgTriArgs a) {
   }
 }
 
-// output channels per k_conv_wgrad_tri block: 64 (3 waves).  NIDT_WG_TRI_NCH=2 gives 128-channel blocks (6 waves)
-// where Cout allows (A/B: slower on every AlexNet layer, conv2 3.28 vs 3.06 ms at 64 clients,
-// profiles/r2_ab_wgrad_tri.txt)
-static int wt_nch(int Cout) {
-  static const int env = env_int("NIDT_WG_TRI_NCH", 1);
-  return (Cout % 128 == 0 && env == 2) ? 2 : 1;
-}
-
 // split factor of k_conv_wgrad_tri: the wgrad cost model over its own tiles (9 x Cin/64 triplets x co blocks x G)
 int conv3d_wgrad_tri_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  // NIDT_WG_TRI_NS=<n>: force the split of the unpadded (conv2) launch (A/B)
-  static const int ns_env = env_int("NIDT_WG_TRI_NS", 0);
-  if (ns_env > 0 && pad == 0) return ns_env;
   const int Mg = out_positions(B, D, H, W, pad);
-  const int nch = wt_nch(Cout);
   // step cost ~1 us per block slot, no fixed term (128-channel blocks at 64 clients, conv2: ns 4 / 6 / 8 / 12 ->
   // 3.27 / 3.28 / 3.09 / 3.12 ms, profiles/r2_ab_wgrad_tri.txt)
   const int U = wt_umax_cap(wgrad_tri_umax(B, D, H, W, pad));
-  const int lds = 2 * (U * 128 + nch * 8192);  // bytes per block; 4 waves per SIMD by registers
-  const int per_cu = std::max(1, std::min(163840 / std::max(lds, 1), 16 / (3 * nch)));
-  const int base = G * (Cout / (64 * nch)) * 9 * (Cin / 64);
+  const int lds = 2 * (U * 128 + 8192);  // bytes per block; 4 waves per SIMD by registers (5 three-wave blocks)
+  const int per_cu = std::max(1, std::min(163840 / std::max(lds, 1), 5));
+  const int base = G * (Cout / 64) * 9 * (Cin / 64);
   const double slots = 256.0 * per_cu;
   const int ns = wgrad_nsplit_base(base, G, Mg, 27 * Cin, Cout, 1.0, 0.0, slots);
   // a single-wave pick (small lockstep groups) ends with its slowest block: every block runs the whole launch, so
@@ -2838,35 +2431,13 @@ void conv3d_wgrad_tri(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad,
                       uintptr_t stream) {
   NIDT_REQUIRE(conv3d_wgrad_tri_ok(B, D, H, W, Cin, Cout, pad), "conv3d_wgrad_tri: shape not eligible");
   NIDT_REQUIRE(stab != 0 && nsplit >= 1, "conv3d_wgrad_tri: needs the step table");
-  const int nch = wt_nch(Cout);
   unsigned nwg;
   const ConvWgTriArgs d = wg_union_args("conv3d_wgrad_tri", x, dy, part, stab, G, B, D, H, W, Cin, Cout, pad, nsplit,
-                                        9 * (Cin / 64), Cout / (64 * nch), &nwg);
+                                        9 * (Cin / 64), Cout / 64, &nwg);
   hipStream_t s = as_stream(stream);
-  const dim3 grid(nwg);
-  // NIDT_WGTRI_LSWZ=1: output-space swizzle of the X rows (A/B: slower, see [LSW])
-  static const int lsw_env = env_int("NIDT_WGTRI_LSWZ", 0);
-  const bool lsw = lsw_env && d.Mg / B >= 64;  // the kernel advances its output-space indices by 64 per step
-  // [SCHED] k-step schedule (kstep_sched): AlexNet conv2-5 weight gradients at 64 clients 4.28 -> 4.24 ms
-  // (profiles/r4_ab_sched_more.txt); NIDT_WGT_SCHED=0: the compiler's schedule (A/B)
-  static const int tsched = env_int("NIDT_WGT_SCHED", 1);
-  // [ADMA] asm-issued stage DMA (NIDT_WGT_ADMA=0: the intrinsic, A/B)
-  static const int tadma = env_int("NIDT_WGT_ADMA", 1);
-  // the output-space swizzle excludes the schedule, and the asm DMA exists with the schedule only
-  const bool sched = tsched && !lsw, adma = sched && tadma;
-  dispatch_int<1, 2>(nch, [&](auto nc) {
-    dispatch_int<80, 96>(wgrad_tri_union(B, D, H, W, pad).U, [&](auto uu) {
-      dispatch_bool(pad != 0, [&](auto pd) {
-        dispatch_bool(lsw, [&](auto lw) {
-          dispatch_bool(sched, [&](auto sc) {
-            dispatch_bool(adma, [&](auto ad) {
-              if constexpr (!(lw.value && sc.value) && (sc.value || !ad.value))
-                hipLaunchKernelGGL((k_conv_wgrad_tri<nc.value, uu.value, pd.value, lw.value, sc.value, ad.value>), grid,
-                                   dim3(192 * nc.value), 0, s, d);
-            });
-          });
-        });
-      });
+  dispatch_int<80, 96>(wgrad_tri_union(B, D, H, W, pad).U, [&](auto uu) {
+    dispatch_bool(pad != 0, [&](auto pd) {
+      hipLaunchKernelGGL((k_conv_wgrad_tri<uu.value, pd.value>), dim3(nwg), dim3(192), 0, s, d);
     });
   });
   NIDT_CHECK(hipGetLastError());
@@ -2886,16 +2457,6 @@ int conv3d_wgrad_slab_ok(int B, int D, int H, int W, int Cin, int Cout, int pad)
   if (conv_out_n(D, pad) < 1 || conv_out_n(H, pad) < 1 || conv_out_n(W, pad) < 1) return 0;
   if (!extents_below_1024(D, H, W, pad)) return 0;
   return ws_u(B, D, H, W, pad) > 0 ? 1 : 0;
-}
-
-// Off by default (NIDT_WG_SLAB=1 opts in where k_conv_wgrad_tri would run): measured slower at 64 clients, conv2 wgrad
-// 3.83 vs 3.03 ms, conv3-5 0.44-0.63 vs 0.36-0.53 ms (profiles/r3_ab_wgrad_slab.txt) — one 12-wave block per CU
-// (114 VGPRs) re-reads the dY tile from LDS in every wave and waits at each step's barrier with no second block
-// to cover it; the triplet kernel's two 3-wave blocks per CU overlap those waits.
-int conv3d_wgrad_slab_pick(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
-  static const int env = env_int("NIDT_WG_SLAB", 0);
-  if (!env || !conv3d_wgrad_slab_ok(B, D, H, W, Cin, Cout, pad)) return 0;
-  return conv3d_wgrad_tri_pick(G, B, D, H, W, Cin, Cout, pad) || env == 2 ? 1 : 0;
 }
 
 int conv3d_wgrad_slab_nsplit(int G, int B, int D, int H, int W, int Cin, int Cout, int pad) {
@@ -2923,12 +2484,8 @@ void conv3d_wgrad_slab(uintptr_t x, uintptr_t dy, uintptr_t part, uintptr_t grad
   const ConvWgTriArgs d = wg_union_args("conv3d_wgrad_slab", x, dy, part, stab, G, B, D, H, W, Cin, Cout, pad, nsplit,
                                         3 * (Cin / 64), Cout / 64, &nwg);
   hipStream_t s = as_stream(stream);
-  // [ADMA] asm-issued stage DMA (k_conv_wgrad_tri); NIDT_WGS_ADMA=0: the intrinsic (A/B)
-  static const int sadma = env_int("NIDT_WGS_ADMA", 1);
   dispatch_bool(pad != 0, [&](auto pd) {
-    dispatch_bool(sadma != 0, [&](auto ad) {
-      hipLaunchKernelGGL((k_conv_wgrad_slab<152, pd.value, ad.value>), dim3(nwg), dim3(768), 0, s, d);
-    });
+    hipLaunchKernelGGL((k_conv_wgrad_slab<152, pd.value>), dim3(nwg), dim3(768), 0, s, d);
   });
   NIDT_CHECK(hipGetLastError());
   k_wgrad_reduce_launch(ptr<const float>(part), nsplit, G, Cout, Cin, 27, ptr<float>(grad), ldg, off, scale, s);
@@ -2985,12 +2542,7 @@ static void conv_wgrad_impl(uintptr_t x, uintptr_t xs, uintptr_t xt, uintptr_t d
     d.x = a.x; d.dy = a.dy; d.ptab = ptr<const int2>(ptab); d.part = a.part;
     d.D = D; d.H = H; d.W = W; d.Cin = Cin; d.Cout = Cout; d.Mg = a.Mg; d.K = a.K; d.nsplit = nsplit; d.G = G;
     d.chunk = ((ceil_div(a.Mg, nsplit) + kWdPos - 1) / kWdPos) * kWdPos;
-    // NIDT_WG_NCH=2: 128-channel blocks where Cout allows (8 waves, the X tile feeds both halves).  Measured slower
-    // than two resident 64-channel blocks per CU (conv2 wgrad 3.91 -> 4.14 ms at 64 clients, 0.505 -> 0.542 ms
-    // at 8; profiles/r2_ab_wgrad_nch.txt): the kernel is latency/barrier bound, not L2->LDS bandwidth bound.
-    static const int nch_env = env_int("NIDT_WG_NCH", 0);
-    const int nch = (Cout % 128 == 0 && nch_env == 2) ? 2 : 1;
-    d.nKT = ceil_div(a.K, kWgKC); d.nCT = Cout / (kWgCO * nch);
+    d.nKT = ceil_div(a.K, kWgKC); d.nCT = Cout / kWgCO;
     d.xclient = (int64_t)B * D * H * W * Cin;
     // [WG-DIRECT] one split: the kernel writes the gradient rows (no fp32 slab round trip, no reduce launch).  The
     // rows are [Cout][Cin][kt] and a block owns 1-4 taps of a channel slice, so for kt > 1 its stores are 4-B
@@ -3005,20 +2557,7 @@ static void conv_wgrad_impl(uintptr_t x, uintptr_t xs, uintptr_t xt, uintptr_t d
                  "conv3d_wgrad: per-client tensors must stay below 2 GiB (32-bit buffer offsets)");
     const int64_t nwg = (int64_t)d.nKT * d.nCT * nsplit * G;
     NIDT_REQUIRE(nwg < (1ll << 31), "conv3d_wgrad: grid too large");
-    // [SCHED] k-step schedule (kstep_sched): AlexNet conv3-5 weight gradients at 8 clients -2.7 %, config 5 12.16 ->
-    // 12.10 s/round (profiles/r4_ab_sched_more.txt); NIDT_WGD_SCHED=0: the compiler's schedule (A/B)
-    static const int wsched = env_int("NIDT_WGD_SCHED", 1);
-    // [ADMA] asm-issued stage DMA (k_conv_wgrad_tri); NIDT_WGD_ADMA=0: the intrinsic (A/B)
-    static const int wadma = env_int("NIDT_WGD_ADMA", 1);
-    dispatch_int<1, 2>(nch, [&](auto nc) {
-      dispatch_bool(wsched != 0, [&](auto sc) {
-        dispatch_bool(wsched && wadma, [&](auto ad) {  // the asm DMA exists with the schedule only
-          if constexpr (sc.value || !ad.value)
-            hipLaunchKernelGGL((k_conv_wgrad_dma<nc.value, sc.value, ad.value>), dim3((unsigned)nwg),
-                               dim3(256 * nc.value), 0, s, d);
-        });
-      });
-    });
+    hipLaunchKernelGGL(k_conv_wgrad_dma, dim3((unsigned)nwg), dim3(256), 0, s, d);
   } else {
     dim3 grid(ceil_div(a.K, kWgKC), Cout / kWgCO, G * nsplit);
     dispatch_bool(xs != 0, [&](auto xf) { hipLaunchKernelGGL((k_conv_wgrad<xf.value>), grid, dim3(256), 0, s, a); });

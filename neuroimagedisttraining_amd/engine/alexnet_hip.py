@@ -103,8 +103,6 @@ class HipAlexNet3D:
             mg = B * (sp[0] + 2 * pad - 2) * (sp[1] + 2 * pad - 2) * (sp[2] + 2 * pad - 2)
             bp = self.m.conv3d_fwd_bp(cin, cout, 0, G, mg)
             npb = self.m.conv3d_fwd_nblocks(B, sp[0], sp[1], sp[2], pad, bp)
-            if self.m.conv3d_fwd_vol_pick(G, B, *sp, cin, cout, pad):  # k_conv_fwd_vol: statistics per sample
-                bp, npb = mg // B, B
             b["st%d" % ci] = e(G, npb, cout, 2, dt=f32)
             b["npb%d" % ci] = npb
             b["bp%d" % ci] = bp
@@ -116,9 +114,6 @@ class HipAlexNet3D:
                 mg = B * (vol[0] + 2 * pd - 2) * (vol[1] + 2 * pd - 2) * (vol[2] + 2 * pd - 2)
                 ks = self.m.conv3d_fwd_ksplit(c_in, c_out, G, mg)
                 b["ks%s%d" % (tag, ci)] = ks
-                if (tag == "f" or train) and self.m.conv3d_fwd_vol_pick(G, B, *vol, c_in, c_out, pd):
-                    # whole-sample union staging (k_conv_fwd_vol): the 5x7x5 conv3-5 forward / data gradient
-                    b["fv%s%d" % (tag, ci)] = True
                 if ks > 1:
                     fp_sz = max(fp_sz, ks * G * mg * c_out)
         b["fpart"] = e(max(fp_sz, 1), dt=f32)
@@ -130,8 +125,6 @@ class HipAlexNet3D:
                 if tag == "d" and not train:
                     continue
                 kname = "ks%s%d" % (tag, ci)
-                if b.get("fv" + kname[2:]):
-                    continue
                 if b[kname] <= 1 and self.m.conv3d_fwd_slab_pick(G, B, *vol, c_in, c_out, pd):
                     # kd-slab union staging (k_conv_fwd_slab): the padded conv2 data gradient
                     tab = e(self.m.conv3d_fwd_slab_table_size(B, *vol, pd), dt=torch.int32)
@@ -145,14 +138,10 @@ class HipAlexNet3D:
             for (ci, bi, cin, cout, pad, sp) in (L2, L3, L4, L5):
                 b["w%dt" % ci] = e(G, cin, 27, cout)
                 b["ns%d" % ci] = self.m.conv3d_wgrad_nsplit(G, B, sp[0], sp[1], sp[2], cin, cout, pad)
-            # wgrad with kd-slab (k_conv_wgrad_slab) or three-tap (k_conv_wgrad_tri) union staging, each with its own
-            # split factor, where the shape allows
+            # wgrad with three-tap (k_conv_wgrad_tri) union staging, with its own split factor, where the shape allows
             for (ci, bi, cin, cout, pad, sp) in (L2, L3, L4, L5):
-                b["wslab%d" % ci] = bool(self.m.conv3d_wgrad_slab_pick(G, B, *sp, cin, cout, pad))
-                b["tri%d" % ci] = not b["wslab%d" % ci] and bool(self.m.conv3d_wgrad_tri_pick(G, B, *sp, cin, cout, pad))
-                if b["wslab%d" % ci]:
-                    b["ns%d" % ci] = self.m.conv3d_wgrad_slab_nsplit(G, B, *sp, cin, cout, pad)
-                elif b["tri%d" % ci]:
+                b["tri%d" % ci] = bool(self.m.conv3d_wgrad_tri_pick(G, B, *sp, cin, cout, pad))
+                if b["tri%d" % ci]:
                     b["ns%d" % ci] = self.m.conv3d_wgrad_tri_nsplit(G, B, *sp, cin, cout, pad)
             wg_sz = max(b["ns%d" % ci] * G * cout * 27 * cin for (ci, bi, cin, cout, pad, sp) in (L2, L3, L4, L5))
             b.update(
@@ -170,10 +159,7 @@ class HipAlexNet3D:
                 b["pt%d" % ci] = e(mg, 2, dt=torch.int32)
                 self.m.conv3d_pos_table(_p(b["pt%d" % ci]), B, sp[0], sp[1], sp[2], pad, st0)
             for (ci, bi, cin, cout, pad, sp) in (L2, L3, L4, L5):
-                if b["wslab%d" % ci]:
-                    b["stab%d" % ci] = e(self.m.conv3d_wgrad_slab_table_size(B, *sp, pad), dt=torch.int32)
-                    self.m.conv3d_wgrad_slab_table(_p(b["stab%d" % ci]), B, *sp, pad, st0)
-                elif b["tri%d" % ci]:
+                if b["tri%d" % ci]:
                     b["stab%d" % ci] = e(self.m.conv3d_wgrad_tri_table_size(B, *sp, pad), dt=torch.int32)
                     self.m.conv3d_wgrad_tri_table(_p(b["stab%d" % ci]), B, *sp, pad, st0)
             # the weight-gradient branch of this launch shape (one per shape: side lanes run shapes concurrently)
@@ -224,14 +210,6 @@ class HipAlexNet3D:
         """conv3d_fwd, or its split-K form when ``b[key]`` (chosen at allocation) is > 1.  With ``theta`` the bias
         of conv ``ci`` is read straight from the flat parameter rows (row stride P), no per-step copy."""
         ks = b[key]
-        if b.get("fv" + key[2:]):  # whole-sample union B operand (k_conv_fwd_vol)
-            if theta is not None:
-                o = self.o["features.%d.bias" % ci]
-                bptr, bld = theta.data_ptr() + 4 * o, theta.stride(0)
-            else:
-                bptr, bld = _p(bias), 0
-            self.m.conv3d_fwd_vol(_p(x), _p(w), bptr, bld, _p(y), _p(stats), G, B, D, H, W, cin, cout, pad, st)
-            return
         ft, fs = b.get("ft" + key), b.get("fs" + key)
         if ft is not None or fs is not None:  # union-staged B operand (k_conv_fwd_slab / k_conv_fwd_tri)
             if theta is not None:
@@ -410,10 +388,6 @@ class HipAlexNet3D:
                 ws.wait_stream(cur)
 
         def wgrad(ci, x, xs, xt, dy, sp, cin, cout, pad):
-            if b.get("wslab%d" % ci) and xs is None:
-                m.conv3d_wgrad_slab(_p(x), _p(dy), _p(b["wgpart"]), _p(grads), P, o["features.%d.weight" % ci], G, B,
-                                    sp[0], sp[1], sp[2], cin, cout, pad, b["ns%d" % ci], 1.0, _p(b["stab%d" % ci]), wst)
-                return
             if b.get("tri%d" % ci) and xs is None:
                 m.conv3d_wgrad_tri(_p(x), _p(dy), _p(b["wgpart"]), _p(grads), P, o["features.%d.weight" % ci], G, B,
                                    sp[0], sp[1], sp[2], cin, cout, pad, b["ns%d" % ci], 1.0, _p(b["stab%d" % ci]), wst)

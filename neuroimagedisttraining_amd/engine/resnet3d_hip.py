@@ -139,41 +139,33 @@ def _zero_bias(G, C, device):
     return z
 
 
-# 3x3x3 stride-1 weight gradients with the union-staged B operand of the AlexNet3D conv2-5 kernels (k_conv_wgrad_slab:
-# one kd-slab union per 64 channels, or k_conv_wgrad_tri: one three-tap union per (kd, kh)) where the shape is eligible;
+# 3x3x3 stride-1 weight gradients with the union-staged B operand of the AlexNet3D conv2-5 kernel (k_conv_wgrad_tri: one
+# three-tap union per (kd, kh)) where the shape is eligible;
 # NIDT_R3D_WG_UNION=0 keeps every layer on the position-table kernel k_conv_wgrad_dma (A/B)
 _WG_UNION = os.environ.get("NIDT_R3D_WG_UNION", "1") != "0"
 _WG_TABS = {}
 
 
 def union_wgrad(x, dy, grads, off, G, B, D, H, W, cin, cout, pad):
-    """dW of a 3x3x3 stride-1 conv into the gradient rows through k_conv_wgrad_slab / k_conv_wgrad_tri; False
-    (nothing launched) when neither applies."""
+    """dW of a 3x3x3 stride-1 conv into the gradient rows through k_conv_wgrad_tri; False (nothing launched) when
+    it does not apply."""
     m = ops.ext()
-    if not _WG_UNION:
+    if not _WG_UNION or not m.conv3d_wgrad_tri_pick(G, B, D, H, W, cin, cout, pad):
         return False
-    if m.conv3d_wgrad_slab_pick(G, B, D, H, W, cin, cout, pad):
-        kind, ns = "slab", m.conv3d_wgrad_slab_nsplit(G, B, D, H, W, cin, cout, pad)
-    elif m.conv3d_wgrad_tri_pick(G, B, D, H, W, cin, cout, pad):
-        kind, ns = "tri", m.conv3d_wgrad_tri_nsplit(G, B, D, H, W, cin, cout, pad)
-    else:
-        return False
-    key = (kind, str(x.device), B, D, H, W, pad)
+    ns = m.conv3d_wgrad_tri_nsplit(G, B, D, H, W, cin, cout, pad)
+    key = (str(x.device), B, D, H, W, pad)
     tab = _WG_TABS.get(key)
     if tab is None:
-        size = (m.conv3d_wgrad_slab_table_size if kind == "slab" else m.conv3d_wgrad_tri_table_size)(B, D, H, W, pad)
-        tab = torch.empty(size, device=x.device, dtype=torch.int32)
-        (m.conv3d_wgrad_slab_table if kind == "slab" else m.conv3d_wgrad_tri_table)(tab.data_ptr(), B, D, H, W, pad,
-                                                                                     _stream())
+        tab = torch.empty(m.conv3d_wgrad_tri_table_size(B, D, H, W, pad), device=x.device, dtype=torch.int32)
+        m.conv3d_wgrad_tri_table(tab.data_ptr(), B, D, H, W, pad, _stream())
         if not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream().synchronize()  # shared with launches on other streams from now on
             _WG_TABS[key] = tab
         else:
             _BRANCH_KEEP.append(tab)
     part = torch.empty(ns * G * cout * 27 * cin, device=x.device, dtype=torch.float32)
-    fn = m.conv3d_wgrad_slab if kind == "slab" else m.conv3d_wgrad_tri
-    fn(x.data_ptr(), dy.data_ptr(), part.data_ptr(), grads.data_ptr(), grads.stride(0), off, G, B, D, H, W, cin, cout,
-       pad, ns, 1.0, tab.data_ptr(), _stream())
+    m.conv3d_wgrad_tri(x.data_ptr(), dy.data_ptr(), part.data_ptr(), grads.data_ptr(), grads.stride(0), off, G, B, D, H,
+                       W, cin, cout, pad, ns, 1.0, tab.data_ptr(), _stream())
     return True
 
 

@@ -27,7 +27,7 @@ FP32_EXACT = 1 << 24      # every integer of magnitude <= 2^24 is an fp32 value
 NNZ_PER_ROW = 256         # default non-zero weights per output row
 
 # ------------------------------------------------------------------------------------------------ shape tables
-# 3x3x3 stride-1 family (conv3d_fwd, _splitk, _tri, _vol, _bld; conv3d_wgrad, _tri, _slab; dgrad through conv3d_fwd)
+# 3x3x3 stride-1 family (conv3d_fwd, _splitk, _tri, _bld; conv3d_wgrad, _tri, _slab; dgrad through conv3d_fwd)
 #   name: (cin, cout, pad, (D, H, W), fused input transform)
 CONV3 = {
     "pad1": (128, 192, 1, (5, 7, 5), False),

@@ -129,16 +129,6 @@ def test_conv2d_slab_choice():
     assert m.conv3d_fwd_slab_table_size(16, 1, 32, 32, 1) == n_bands * (2 * 384 + 256)
 
 
-def test_vol_kernel_rule():
-    """Whole-sample union kernel (k_conv_fwd_vol): padded sample <= 448 rows and <= 256 output positions; opt-in."""
-    m = _ext()
-    assert m.conv3d_fwd_vol_ok(16, 5, 7, 5, 128, 192, 1) == 1      # AlexNet conv3: 7x9x7 = 441 rows, 175 positions
-    assert m.conv3d_fwd_vol_ok(16, 5, 7, 5, 192, 128, 1) == 1
-    assert m.conv3d_fwd_vol_ok(16, 6, 8, 7, 64, 64, 1) == 0        # 8x10x9 = 720 padded rows
-    assert m.conv3d_fwd_vol_ok(16, 5, 7, 5, 96, 128, 1) == 0       # channels not a multiple of 64
-    assert m.conv3d_fwd_vol_pick(64, 16, 5, 7, 5, 128, 192, 1) == 0  # off unless NIDT_FWD_VOL=1
-
-
 # Host decisions of the conv launchers, recorded from the build before the launch dispatch was rewritten (default
 # environment: no NIDT_* switch set): function -> (arguments, result; a string = the call raises ValueError with that
 # text).  Shapes: the AlexNet3D conv2 / conv2 data gradient / conv3 / conv4 / conv5 geometries above at 1, 8 and 64
@@ -152,10 +142,6 @@ _PINNED = {
     "conv3d_fwd_slab_ok": [
         ((16, 19, 23, 19, 64, 128, 0), 1), ((16, 17, 21, 17, 128, 64, 2), 1), ((16, 5, 7, 5, 128, 192, 1), 0),
         ((16, 5, 7, 5, 192, 192, 1), 0), ((16, 5, 7, 5, 192, 128, 1), 0), ((4, 31, 37, 31, 64, 64, 1), 1),
-    ],
-    "conv3d_fwd_vol_ok": [
-        ((16, 19, 23, 19, 64, 128, 0), 0), ((16, 17, 21, 17, 128, 64, 2), 0), ((16, 5, 7, 5, 128, 192, 1), 1),
-        ((16, 5, 7, 5, 192, 192, 1), 1), ((16, 5, 7, 5, 192, 128, 1), 1), ((4, 31, 37, 31, 64, 64, 1), 0),
     ],
     "conv3d_wgrad_tri_ok": [
         ((16, 19, 23, 19, 64, 128, 0), 1), ((16, 17, 21, 17, 128, 64, 2), 1), ((16, 5, 7, 5, 128, 192, 1), 1),
@@ -224,15 +210,6 @@ _PINNED = {
         ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
         ((1, 4, 31, 37, 31, 64, 64, 1), 1), ((8, 4, 31, 37, 31, 64, 64, 1), 1),
     ],
-    "conv3d_fwd_vol_pick": [
-        ((1, 16, 19, 23, 19, 64, 128, 0), 0), ((8, 16, 19, 23, 19, 64, 128, 0), 0),
-        ((64, 16, 19, 23, 19, 64, 128, 0), 0), ((1, 16, 17, 21, 17, 128, 64, 2), 0),
-        ((8, 16, 17, 21, 17, 128, 64, 2), 0), ((64, 16, 17, 21, 17, 128, 64, 2), 0),
-        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 0), ((64, 16, 5, 7, 5, 128, 192, 1), 0),
-        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 0), ((64, 16, 5, 7, 5, 192, 192, 1), 0),
-        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
-        ((1, 4, 31, 37, 31, 64, 64, 1), 0), ((8, 4, 31, 37, 31, 64, 64, 1), 0),
-    ],
     "conv3d_wgrad_tri_pick": [
         ((1, 16, 19, 23, 19, 64, 128, 0), 1), ((8, 16, 19, 23, 19, 64, 128, 0), 1),
         ((64, 16, 19, 23, 19, 64, 128, 0), 1), ((1, 16, 17, 21, 17, 128, 64, 2), 1),
@@ -250,15 +227,6 @@ _PINNED = {
         ((1, 16, 5, 7, 5, 192, 192, 1), 5), ((8, 16, 5, 7, 5, 192, 192, 1), 1), ((64, 16, 5, 7, 5, 192, 192, 1), 1),
         ((1, 16, 5, 7, 5, 192, 128, 1), 5), ((8, 16, 5, 7, 5, 192, 128, 1), 2), ((64, 16, 5, 7, 5, 192, 128, 1), 1),
         ((1, 4, 31, 37, 31, 64, 64, 1), 64), ((8, 4, 31, 37, 31, 64, 64, 1), 14),
-    ],
-    "conv3d_wgrad_slab_pick": [
-        ((1, 16, 19, 23, 19, 64, 128, 0), 0), ((8, 16, 19, 23, 19, 64, 128, 0), 0),
-        ((64, 16, 19, 23, 19, 64, 128, 0), 0), ((1, 16, 17, 21, 17, 128, 64, 2), 0),
-        ((8, 16, 17, 21, 17, 128, 64, 2), 0), ((64, 16, 17, 21, 17, 128, 64, 2), 0),
-        ((1, 16, 5, 7, 5, 128, 192, 1), 0), ((8, 16, 5, 7, 5, 128, 192, 1), 0), ((64, 16, 5, 7, 5, 128, 192, 1), 0),
-        ((1, 16, 5, 7, 5, 192, 192, 1), 0), ((8, 16, 5, 7, 5, 192, 192, 1), 0), ((64, 16, 5, 7, 5, 192, 192, 1), 0),
-        ((1, 16, 5, 7, 5, 192, 128, 1), 0), ((8, 16, 5, 7, 5, 192, 128, 1), 0), ((64, 16, 5, 7, 5, 192, 128, 1), 0),
-        ((1, 4, 31, 37, 31, 64, 64, 1), 0), ((8, 4, 31, 37, 31, 64, 64, 1), 0),
     ],
     "conv3d_wgrad_slab_nsplit": [
         ((1, 16, 19, 23, 19, 64, 128, 0), 42), ((8, 16, 19, 23, 19, 64, 128, 0), 5),
@@ -325,7 +293,7 @@ _PINNED = {
 
 def test_host_decisions_pinned():
     m = _ext()
-    assert sum(len(v) for v in _PINNED.values()) == 308
+    assert sum(len(v) for v in _PINNED.values()) == 268
     for fn, cases in _PINNED.items():
         for args, want in cases:
             if isinstance(want, str):

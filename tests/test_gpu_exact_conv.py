@@ -101,8 +101,6 @@ def _fwd3_params():
     for name in L.CONV3:
         for G, B in L.CONV3_GB[name]:
             kernels = ["fwd", "bld", "tri"] + ["splitk%d" % k for k in L.SPLITK3]
-            if name != "pad2":  # the padded sample of pad 2 (9x11x9 rows) exceeds the whole-sample kernel's union
-                kernels.append("vol")
             out += [(name, G, B, k) for k in kernels]
     for name in L.SLAB3:
         out += [(name,) + L.SLAB3_GB + (k,) for k in ("fwd", "tri", "slab")]
@@ -112,7 +110,7 @@ def _fwd3_params():
 @pytest.mark.parametrize("name,G,B,kernel", _fwd3_params())
 def test_conv3_forward_exact(name, G, B, kernel):
     """conv3d_fwd (LDS-DMA per-tap kernel at its 64-, 128- and 256-position blocks; the register-staged kernel with the
-    fused input transform), conv3d_fwd_bld, conv3d_fwd_splitk, conv3d_fwd_tri, conv3d_fwd_slab and conv3d_fwd_vol, with
+    fused input transform), conv3d_fwd_bld, conv3d_fwd_splitk, conv3d_fwd_tri and conv3d_fwd_slab, with
     and without bias, against one fp64 reference per case."""
     m = _m()
     c = L.conv3(name, G, B, grads=name in L.SLAB3)  # the slab cases are the backward tests' cases too
@@ -158,19 +156,14 @@ def test_conv3_forward_exact(name, G, B, kernel):
                          cout, pad, tab.data_ptr(), _st())
         m.conv3d_fwd_tri(x.data_ptr(), w.data_ptr(), 0, 0, y0.data_ptr(), 0, G, B, *sp, cin, cout, pad, tab.data_ptr(),
                          _st())
-    elif kernel == "slab":
-        assert m.conv3d_fwd_slab_ok(B, *sp, cin, cout, pad)
+    else:
+        assert kernel == "slab" and m.conv3d_fwd_slab_ok(B, *sp, cin, cout, pad)
         tab = torch.empty(m.conv3d_fwd_slab_table_size(B, *sp, pad), device=DEV, dtype=torch.int32)
         m.conv3d_fwd_slab_table(tab.data_ptr(), B, *sp, pad, _st())
         m.conv3d_fwd_slab(x.data_ptr(), w.data_ptr(), bias.data_ptr(), 0, y.data_ptr(), stats.data_ptr(), G, B, *sp,
                           cin, cout, pad, tab.data_ptr(), _st())
         m.conv3d_fwd_slab(x.data_ptr(), w.data_ptr(), 0, 0, y0.data_ptr(), 0, G, B, *sp, cin, cout, pad,
                           tab.data_ptr(), _st())
-    else:
-        assert kernel == "vol" and m.conv3d_fwd_vol_ok(B, *sp, cin, cout, pad)
-        m.conv3d_fwd_vol(x.data_ptr(), w.data_ptr(), bias.data_ptr(), 0, y.data_ptr(), stats.data_ptr(), G, B, *sp, cin,
-                         cout, pad, _st())
-        m.conv3d_fwd_vol(x.data_ptr(), w.data_ptr(), 0, 0, y0.data_ptr(), 0, G, B, *sp, cin, cout, pad, _st())
     torch.cuda.synchronize()
     L.assert_exact(y0, _cs(c.y, c), AX3)
     L.assert_exact(y, _cs(L.y_with_bias(c), c), AX3)
@@ -238,8 +231,7 @@ def test_conv3_wgrad_exact(name, G, B, kernel, ns):
 def _dgrad3_params():
     out = []
     for name in L.CONV3:
-        kernels = ["fwd", "tri"] + (["vol"] if name != "pad0" else [])  # pad0's dgrad reads a 9x11x9 padded sample
-        out += [(name, G, B, k) for G, B in L.CONV3_BWD_GB for k in kernels]
+        out += [(name, G, B, k) for G, B in L.CONV3_BWD_GB for k in ("fwd", "tri")]
     for name in L.SLAB3:
         out += [(name,) + L.SLAB3_GB + (k,) for k in ("fwd", "slab")]
     return out
@@ -268,15 +260,12 @@ def test_conv3_dgrad_through_forward_exact(name, G, B, kernel):
         m.conv3d_fwd_tri_table(tab.data_ptr(), B, *do, p2, _st())
         m.conv3d_fwd_tri(dy.data_ptr(), wt.data_ptr(), 0, 0, dx.data_ptr(), 0, G, B, *do, cout, cin, p2, tab.data_ptr(),
                          _st())
-    elif kernel == "slab":
-        assert m.conv3d_fwd_slab_ok(B, *do, cout, cin, p2)
+    else:
+        assert kernel == "slab" and m.conv3d_fwd_slab_ok(B, *do, cout, cin, p2)
         tab = torch.empty(m.conv3d_fwd_slab_table_size(B, *do, p2), device=DEV, dtype=torch.int32)
         m.conv3d_fwd_slab_table(tab.data_ptr(), B, *do, p2, _st())
         m.conv3d_fwd_slab(dy.data_ptr(), wt.data_ptr(), 0, 0, dx.data_ptr(), 0, G, B, *do, cout, cin, p2,
                           tab.data_ptr(), _st())
-    else:
-        assert kernel == "vol" and m.conv3d_fwd_vol_ok(B, *do, cout, cin, p2)
-        m.conv3d_fwd_vol(dy.data_ptr(), wt.data_ptr(), 0, 0, dx.data_ptr(), 0, G, B, *do, cout, cin, p2, _st())
     torch.cuda.synchronize()
     L.assert_exact(wp, c.w.view(G, cout, cin, 27).permute(0, 1, 3, 2), ("client", "cout", "tap", "cin"))
     L.assert_exact(wt, c.w.view(G, cout, cin, 27).flip(3).permute(0, 2, 3, 1), ("client", "cin", "tap", "cout"))
