@@ -24,6 +24,13 @@ void rows_diff_norm(uintptr_t rows, uintptr_t ref, int64_t C, int64_t P, int64_t
 void clipped_rows_sum(uintptr_t rows, uintptr_t ref, uintptr_t wts, uintptr_t norm, uintptr_t cids, int64_t C,
                       int64_t P, int64_t stride, float norm_bound, float stddev, uint64_t seed, uintptr_t mbits,
                       uintptr_t out, uintptr_t stream);
+// robust.hip
+void rows_order_mean(uintptr_t rows, int64_t stride, uintptr_t ridx, int64_t K, int64_t n, int64_t lo, int64_t hi,
+                     uintptr_t out, uintptr_t stream);
+int64_t rows_pair_sqdist_workspace(int64_t K, int64_t n);
+void rows_pair_sqdist(uintptr_t rows, int64_t stride, uintptr_t ridx, int64_t K, int64_t n, uintptr_t part,
+                      uintptr_t D, int64_t accumulate, uintptr_t stream);
+void krum_select(uintptr_t D, int64_t K, int64_t f, int64_t multi, uintptr_t sel, uintptr_t score, uintptr_t stream);
 // optim.hip
 void local_opt(uintptr_t w, uintptr_t g, uintptr_t buf, int64_t ld, uintptr_t mbits, int64_t mstride, int mask_mode,
                uintptr_t ref, int64_t ref_ld, float mu, uintptr_t pref, int64_t pref_ld, float lamda, uintptr_t part,
@@ -278,6 +285,10 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(rows_diff_norm_blocks);
   DEF(rows_diff_norm);
   DEF(clipped_rows_sum);
+  DEF(rows_order_mean);
+  DEF(rows_pair_sqdist_workspace);
+  DEF(rows_pair_sqdist);
+  DEF(krum_select);
   DEF(rows_nnz_blocks);
   DEF(rows_nnz);
   DEF(broadcast_row);

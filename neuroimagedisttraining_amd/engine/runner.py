@@ -1109,14 +1109,30 @@ class FLRunner:
         return dict(defense_clipped=int(round(float(r[0]))), defense_max_ratio=float(r[1]))
 
     def aggregate_robust(self, sampled):
-        """Byzantine-robust aggregation (BASELINE config 4): every sampled client's (params, buffers) row is
-        all-gathered to every rank (xGMI all-gather of K x (P+Q) fp32; 128 x 10.3 MB = 1.3 GB fits HBM
-        easily), then Krum / Multi-Krum / coordinate median / trimmed mean run on device with the same
-        deterministic result on all ranks (``core/robustness.py``).  BN buffers follow the selected clients
-        for Krum and are coordinate-aggregated otherwise."""
-        from ..core import robustness as R
+        """Byzantine-robust aggregation (BASELINE config 4): Krum / Multi-Krum / coordinate median / trimmed mean
+        over the sampled clients, the same deterministic result on all ranks.  BN buffers follow the selected
+        clients for Krum and are coordinate-aggregated otherwise.
+
+        On the device the rows are aggregated where they lie by the kernels of ``robust.hip``
+        (``engine/robust.py``: one process reads ``theta`` / ``bufs`` in place, several ranks gather one column
+        chunk at a time), under one total order that puts NaN last and breaks ties by client id.  On the CPU every
+        sampled client's (params, buffers) row is all-gathered to every rank and handed to ``core/robustness.py``
+        (torch's sort / median / topk semantics)."""
         rows, loc = self._local_rows(sampled)
         W = self.P + self.Q
+        kind = self.cfg.aggregator
+        if self.device.type == "cuda" and ops.available():
+            from . import robust as RB
+            K = len(sampled)
+            res = RB.aggregate(kind, self.theta, self.bufs, self.P, self.Q, rows, loc, sampled, self.owner, self.info,
+                               self.w_global, self.b_global, f=self.cfg.byzantine_f,
+                               multi=self.cfg.multikrum_m or max(1, K - self.cfg.byzantine_f),
+                               trim_ratio=self.cfg.trim_ratio, hip=True)
+            if res["sel"] is not None:
+                self.stat_info["krum_selected"] = res["sel"]
+            self.stat_info["aggregate_elems"] = int(K * W)
+            return
+        from ..core import robustness as R
         # one record per client: [id, params, buffers]; every rank knows how many sampled clients each rank owns,
         # so the gather needs no size exchange (no host round trip)
         lm = torch.cat([self._to_dev(loc, torch.float32).view(-1, 1), self.theta[rows, :self.P],
@@ -1125,7 +1141,6 @@ class FLRunner:
         allrows = rt.all_gather_sized(lm.reshape(-1).contiguous(), per_rank, self.info).view(-1, 1 + W)
         order = torch.argsort(allrows[:, 0])  # deterministic client order on every rank
         M = allrows[:, 1:].index_select(0, order)
-        kind = self.cfg.aggregator
         if kind in ("krum", "multikrum"):
             m = 1 if kind == "krum" else (self.cfg.multikrum_m or max(1, M.shape[0] - self.cfg.byzantine_f))
             agg, _ = R.krum(M, f=self.cfg.byzantine_f, multi=m)
