@@ -575,7 +575,9 @@ __global__ __launch_bounds__(512, 2) void k_stem_wgrad4(StemDims d, const uint8_
       rlo[h] = rhi[h] = make_uint2(0, 0);
       if (yrow < d.PY) {
         const uint8_t* row = xq + ((int64_t)n * 8 + s_r[h]) * vox + ((int64_t)(od + s_jd[h]) * d.PY + yrow) * d.PX;
-        rlo[h] = *reinterpret_cast<const uint2*>(row + s_p0[h]);
+        // PX is a multiple of 8 (the dispatch) but may be below 64: words at or past PX belong to the next row, or lie
+        // behind xq for the last rows of the last sample; they only meet positions >= OW, whose dy is zero
+        if (s_p0[h] < d.PX) rlo[h] = *reinterpret_cast<const uint2*>(row + s_p0[h]);
         if (s_p0[h] + 8 < d.PX) rhi[h] = *reinterpret_cast<const uint2*>(row + s_p0[h] + 8);
       }
     }
