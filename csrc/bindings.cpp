@@ -31,6 +31,16 @@ int64_t rows_pair_sqdist_workspace(int64_t K, int64_t n);
 void rows_pair_sqdist(uintptr_t rows, int64_t stride, uintptr_t ridx, int64_t K, int64_t n, uintptr_t part,
                       uintptr_t D, int64_t accumulate, uintptr_t stream);
 void krum_select(uintptr_t D, int64_t K, int64_t f, int64_t multi, uintptr_t sel, uintptr_t score, uintptr_t stream);
+// secagg.hip
+int64_t secagg_blocks(int64_t P);
+void secagg_upload(uintptr_t rows, int64_t stride, uintptr_t ridx, uintptr_t cids, uintptr_t wts, uintptr_t poff,
+                   uintptr_t pid, uintptr_t pkey, int64_t C, int64_t P, int64_t round, int64_t seg, double S, double B,
+                   uintptr_t out, uintptr_t cnt, uintptr_t stream);
+void secagg_masked_sum(uintptr_t rows, int64_t stride, uintptr_t ridx, uintptr_t cids, uintptr_t wts, uintptr_t poff,
+                       uintptr_t pid, uintptr_t pkey, int64_t C, int64_t P, int64_t round, int64_t seg, double S,
+                       double B, uintptr_t out, uintptr_t cnt, uintptr_t stream);
+void secagg_finish(uintptr_t sum, int64_t P, uintptr_t sid, uintptr_t did, uintptr_t pkey, int64_t npair,
+                   int64_t round, int64_t seg, double S, double a, uintptr_t out, uintptr_t stream);
 // optim.hip
 void local_opt(uintptr_t w, uintptr_t g, uintptr_t buf, int64_t ld, uintptr_t mbits, int64_t mstride, int mask_mode,
                uintptr_t ref, int64_t ref_ld, float mu, uintptr_t pref, int64_t pref_ld, float lamda, uintptr_t part,
@@ -289,6 +299,10 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(rows_pair_sqdist_workspace);
   DEF(rows_pair_sqdist);
   DEF(krum_select);
+  DEF(secagg_blocks);
+  DEF(secagg_upload);
+  DEF(secagg_masked_sum);
+  DEF(secagg_finish);
   DEF(rows_nnz_blocks);
   DEF(rows_nnz);
   DEF(broadcast_row);

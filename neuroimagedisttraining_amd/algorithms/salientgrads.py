@@ -103,7 +103,12 @@ class SailentGradsAPI(APIBase):
                 w_locals.append((client.get_sample_number(), w_per))
                 self.stat_info["sum_training_flops"] += flops
                 self.stat_info["sum_comm_params"] += comm
-            w_global = self._aggregate(w_locals)
+            if (getattr(self.args, "aggregator", "fedavg") or "fedavg") == "secure":
+                from .fedavg import secure_aggregate
+                w_global, self._secagg_keys = secure_aggregate(self.args, self.stat_info, w_locals, round_idx, idx,
+                                                               getattr(self, "_secagg_keys", None))
+            else:
+                w_global = self._aggregate(w_locals)
             self.stat_info["global_sparsity"] = model_sparsity(w_global)
             if getattr(self.args, "frequency_of_the_test", 1) and (round_idx % max(1, self.args.frequency_of_the_test) == 0):
                 self._test_on_all_clients(w_global, w_per_mdls, round_idx)

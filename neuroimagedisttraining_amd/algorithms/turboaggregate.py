@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from ..engine.masks import counter_mask, mod_mersenne31  # noqa: F401 (the prg="counter" mask PRG)
+
 P_DEFAULT = 2 ** 31 - 1  # Mersenne prime
 
 
@@ -201,50 +203,145 @@ def dequantize(q, scale, p):
     return q.astype(np.float64) / scale
 
 
-class TurboAggregateTrainer:
-    """Secure FedAvg over flat parameter vectors with pairwise masking and BGW-protected secret keys."""
+def saturation_bound(K, p=P_DEFAULT):
+    """Largest ``|q|`` one of ``K`` participants may send so that the sum of K values stays decodable."""
+    return ((p - 1) // 2) // max(1, int(K))
 
-    def __init__(self, n_clients, p=P_DEFAULT, g=7, scale=2 ** 16, threshold=None, seed=0):
-        self.n, self.p, self.g, self.scale = n_clients, p, g, scale
+
+def quantize_saturated(vec, weight, scale, K, p=P_DEFAULT):
+    """(residues int64 in [0, p), events): ``q = rint((double(vec) * weight) * scale)`` (round half to even, the bits
+    of :func:`quantize` on fp64 input), ``|q|`` saturated at :func:`saturation_bound` of ``K`` participants, a
+    non-finite value -> 0; ``events`` counts both."""
+    return quantize_bounded(vec, weight, scale, saturation_bound(K, p), p)
+
+
+def quantize_bounded(vec, weight, scale, B, p=P_DEFAULT):
+    """:func:`quantize_saturated` with the bound given."""
+    B = float(B)
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = (np.asarray(vec).astype(np.float64) * float(weight)) * float(scale)
+        fin = np.isfinite(x)
+        r = np.round(np.where(fin, x, 0.0))
+    events = int((~fin).sum() + (np.abs(r) > B).sum())
+    return np.clip(r, -B, B).astype(np.int64) % p, events
+
+
+class TurboAggregateTrainer:
+    """Secure FedAvg over flat parameter vectors with pairwise masking and BGW-protected secret keys.
+
+    ``prg="mt"`` (default): a pair's mask is a Mersenne-Twister stream seeded by its key, the same in every round.
+    ``prg="counter"``: :func:`counter_mask` keyed by (key, round, segment, coordinate) and saturating quantisation
+    (:func:`quantize_saturated`) - the protocol of ``csrc/kernels/secagg.hip``, whose rows :meth:`client_upload`
+    then reproduces bit for bit."""
+
+    def __init__(self, n_clients, p=P_DEFAULT, g=7, scale=2 ** 16, threshold=None, seed=0, prg="mt"):
+        if prg not in ("mt", "counter"):
+            raise ValueError("prg %r: one of mt | counter" % (prg,))
+        if prg == "counter" and p != P_DEFAULT:
+            raise ValueError("prg=counter is defined over p = 2^31 - 1 only")
+        self.n, self.p, self.g, self.scale, self.prg = n_clients, p, g, scale, prg
         self.T = threshold if threshold is not None else max(1, n_clients // 2)
         self.rng = np.random.RandomState(seed)
         self.sk = self.rng.randint(1, p - 1, size=n_clients)
         self.pk = [my_pk_gen(s, p, g) for s in self.sk]
         # each client's secret key is Shamir-shared with everyone (for dropout recovery)
         self.sk_shares = [BGW_encoding(np.array([[s]]), n_clients, self.T, p, self.rng) for s in self.sk]
+        self.saturated = 0  # prg="counter": saturated + non-finite values over all uploads so far
 
-    def _mask(self, i, j, d):
-        key = my_key_agreement(self.sk[i], self.pk[j], self.p, self.g)
-        r = np.random.RandomState(key % (2 ** 32)).randint(self.p, size=d).astype(np.int64)
+    def pair_key(self, i, j):
+        return my_key_agreement(self.sk[i], self.pk[j], self.p, self.g)
+
+    def _stream(self, key, d, round, seg):  # noqa: A002
+        if self.prg == "counter":
+            return counter_mask(key, round, seg, np.arange(d, dtype=np.uint64))
+        return np.random.RandomState(key % (2 ** 32)).randint(self.p, size=d).astype(np.int64)
+
+    def _mask(self, i, j, d, round=0, seg=0):  # noqa: A002
+        r = self._stream(self.pair_key(i, j), d, round, seg)
         return r if i < j else (-r) % self.p
 
-    def client_upload(self, i, vec, weight):
+    def client_upload(self, i, vec, weight, round=0, seg=0, peers=None):  # noqa: A002
+        """Client i's masked vector.  ``prg="counter"``: ``round`` / ``seg`` key the masks and ``peers`` (default:
+        every other client) are the round's other participants; K = len(peers) + 1 sets the saturation bound."""
         d = vec.size
-        y = quantize(vec * weight, self.scale, self.p)
-        for j in range(self.n):
-            if j != i:
-                y = (y + self._mask(i, j, d)) % self.p
+        peers = [j for j in range(self.n) if j != i] if peers is None else [int(j) for j in peers if int(j) != i]
+        if self.prg == "counter":
+            y, ev = quantize_saturated(vec, weight, self.scale, len(peers) + 1, self.p)
+            self.saturated += ev
+        else:
+            y = quantize(vec * weight, self.scale, self.p)
+        for j in peers:
+            y = (y + self._mask(i, j, d, round, seg)) % self.p
         return y
 
-    def server_aggregate(self, uploads, dropped=()):
-        """``uploads``: dict client -> masked vector.  Masks of dropped clients are removed by reconstructing
-        their secret keys from BGW shares held by the survivors."""
+    def reconstruct_sks(self, dropped, alive):
+        """{k: client k's secret key} for the ``dropped`` clients, from the BGW shares the first T + 1 of the ``alive``
+        clients hold."""
+        hold = sorted(int(c) for c in alive)[:self.T + 1]
+        lam = [int(v) for v in gen_BGW_lambda_s([i + 1 for i in hold], self.p)]
+        out = {}
+        for k in dropped:
+            sk_k = sum(int(self.sk_shares[int(k)][i][0, 0]) * l for i, l in zip(hold, lam)) % self.p
+            assert sk_k == int(self.sk[int(k)])
+            out[int(k)] = sk_k
+        return out
+
+    def server_sum(self, uploads, dropped=(), round=0, seg=0):  # noqa: A002
+        """Sum of the uploads mod p with the survivors' masks towards the ``dropped`` clients removed: residues."""
         alive = sorted(uploads)
         d = next(iter(uploads.values())).size
         s = np.zeros(d, dtype=np.int64)
         for i in alive:
             s = (s + uploads[i]) % self.p
+        sks = self.reconstruct_sks(dropped, alive)
         for k in dropped:
-            shares = np.stack([self.sk_shares[k][i] for i in alive[:self.T + 1]])
-            sk_k = int(BGW_decoding(shares, alive[:self.T + 1], self.p)[0, 0])
-            assert sk_k == int(self.sk[k])
+            sk_k = sks[int(k)]
             for i in alive:  # the survivors' masks with k did not cancel: remove them
-                key = my_key_agreement(sk_k, self.pk[i], self.p, self.g)
-                r = np.random.RandomState(key % (2 ** 32)).randint(self.p, size=d).astype(np.int64)
-                m_ik = (-r) % self.p if i > k else r  # mask client i added for pair (i, k)
-                m_ik = r if i < k else (-r) % self.p
+                r = self._stream(my_key_agreement(sk_k, self.pk[i], self.p, self.g), d, round, seg)
+                m_ik = r if i < k else (-r) % self.p  # mask client i added for pair (i, k)
                 s = (s - m_ik) % self.p
+        return s
+
+    def server_aggregate(self, uploads, dropped=(), round=0, seg=0, alive_weight=1.0):  # noqa: A002
+        """``uploads``: dict client -> masked vector.  Masks of dropped clients are removed by reconstructing
+        their secret keys from BGW shares held by the survivors.  ``prg="counter"``: the result is
+        ``float32(double(c) / scale / alive_weight)`` (``alive_weight`` = the survivors' share of the weights)."""
+        s = self.server_sum(uploads, dropped, round, seg)
+        if self.prg == "counter":
+            return ((dequantize(s, 1, self.p) / float(self.scale)) / float(alive_weight)).astype(np.float32)
         return dequantize(s, self.scale, self.p)
+
+
+def secure_state_average(trainer, w_locals, client_ids, round_idx=0, dropped=(), is_param=None):
+    """Sample-weighted mean of ``w_locals`` (``[(n_samples, state_dict)]`` of the participants ``client_ids``) through
+    a ``prg="counter"`` trainer: the entries ``is_param`` keeps travel as segment 0 and the others (BN statistics) as
+    segment 1, each flattened in state order; the ``dropped`` participants never upload and their masks are recovered.
+    The client-batched executor's ``--aggregator secure`` computes the same bits.  Every entry comes back as float32,
+    the format the server decodes to (``weighted_average`` likewise returns integer entries such as
+    ``num_batches_tracked`` as floats)."""
+    import torch
+    ids = [int(c) for c in client_ids]
+    keys = list(w_locals[0][1].keys())
+    is_param = is_param or (lambda k: True)
+    gone = set(int(c) for c in dropped)
+    n_tot = float(sum(n for n, _ in w_locals))
+    a = float(sum(n for (n, _), c in zip(w_locals, ids) if c not in gone)) / n_tot
+    out = {}
+    for seg, ks in enumerate(([k for k in keys if is_param(k)], [k for k in keys if not is_param(k)])):
+        if not ks:
+            continue
+        uploads = {}
+        for (n, sd), c in zip(w_locals, ids):
+            if c not in gone:
+                vec = np.concatenate([sd[k].detach().reshape(-1).float().cpu().numpy() for k in ks])
+                uploads[c] = trainer.client_upload(c, vec, n / n_tot, round=round_idx, seg=seg, peers=ids)
+        agg = trainer.server_aggregate(uploads, dropped=sorted(gone), round=round_idx, seg=seg, alive_weight=a)
+        o = 0
+        for k in ks:
+            t = w_locals[0][1][k]
+            out[k] = torch.from_numpy(agg[o:o + t.numel()].copy()).view(t.shape).to(t.device)
+            o += t.numel()
+    return {k: out[k] for k in keys}
 
 
 class TA_Client:  # noqa: N801 (reference name)

@@ -21,6 +21,11 @@ the reference entry points.  Added flags:
   SalientGrads mask only on the kept coordinates); on the eager path ``RobustAggregator`` itself with
   ``torch.randn``.  FedAvg-style aggregation only: not with ``--aggregator`` other than ``fedavg``, ``--update_topk``
   or the personalized algorithms (``ValueError``).
+* ``--aggregator secure``, ``--secagg_scale``, ``--secagg_dropout``, ``--secagg_threshold``, ``--secagg_fuse``: FedAvg's
+  mean as a secure aggregation over Z_p (quantised updates under pairwise masks, BGW recovery of the clients that drop
+  after the key setup).  On the HIP executor three streaming kernels over the client rows (``engine/secagg.py``); on
+  the eager path ``TurboAggregateTrainer(prg="counter")``, which computes the same bits.  sailentgrads / fedavg /
+  fedprox only, and not with ``--defense_type`` or ``--update_topk`` (``ValueError``).
 * ``--checkpoint_dir`` / ``--checkpoint_every`` / ``--keep_last`` / ``--resume`` for the HIP executor (background-written,
   indexed, world-size independent checkpoints: ``utils/checkpoint.py``).
 
@@ -137,6 +142,13 @@ def add_args(parser, algo):
       help="norm_diff_clipping: clip each client's update to --norm_bound; weak_dp: clip, then N(0, --stddev^2) noise")
     a("--norm_bound", type=float, default=5.0)
     a("--stddev", type=float, default=0.025)
+    a("--secagg_scale", type=int, default=2 ** 16, help="--aggregator secure: fixed-point scale of the updates")
+    a("--secagg_dropout", type=float, default=0.0,
+      help="--aggregator secure: fraction of the sampled clients that drop after the key setup")
+    a("--secagg_threshold", type=int, default=0,
+      help="--aggregator secure: BGW threshold of the shared secret keys (0 = sampled clients // 2)")
+    a("--secagg_fuse", type=int, default=1,
+      help="--aggregator secure: 0 materialises every client's masked upload (the protocol's real cost, same bits)")
     a("--group", type=int, default=0)
     a("--checkpoint_dir", type=str, default="")
     a("--checkpoint_every", type=int, default=1,
@@ -383,6 +395,9 @@ def fl_config(args, algo):
     if defense != "none" and algo not in DEFENDED_ALGOS:
         raise ValueError("defense_type=%s cannot be combined with algorithm=%s (only sailentgrads / fedavg / fedprox)"
                          % (defense, algo))
+    if g("aggregator", "fedavg") == "secure" and algo not in DEFENDED_ALGOS:
+        raise ValueError("aggregator=secure cannot be combined with algorithm=%s (only sailentgrads / fedavg / fedprox)"
+                         % (algo,))
     return FLConfig(comm_round=args.comm_round, epochs=args.epochs, batch_size=args.batch_size, lr=args.lr,
                     lr_decay=args.lr_decay, wd=args.wd, momentum=args.momentum, frac=args.frac,
                     dense_ratio=g("dense_ratio", 1.0), itersnip_iteration=g("itersnip_iteration", 1),
@@ -400,7 +415,9 @@ def fl_config(args, algo):
                     erk_power_scale=g("erk_power_scale", 1.0), save_masks=bool(g("save_masks", False)),
                     dispfl_aggregate=bool(g("dispfl_aggregate", 0)), each_prune_ratio=g("each_prune_ratio", 0.05),
                     dist_thresh=g("dist_thresh", 1e-4), acc_thresh=g("acc_thresh", 0.5),
-                    defense_type=defense, norm_bound=g("norm_bound", 5.0), stddev=g("stddev", 0.025))
+                    defense_type=defense, norm_bound=g("norm_bound", 5.0), stddev=g("stddev", 0.025),
+                    secagg_scale=g("secagg_scale", 2 ** 16), secagg_dropout=g("secagg_dropout", 0.0),
+                    secagg_threshold=g("secagg_threshold", 0) or 0, secagg_fuse=bool(g("secagg_fuse", 1)))
 
 
 def image_cohort(args, info, with_val=False):
@@ -567,7 +584,7 @@ def main(algo, argv=None):
     args = parser.parse_args(argv)
     args.algo = algo
     args.identity = identity(args, algo)
-    if args.defense_type != "none":
+    if args.defense_type != "none" or args.aggregator == "secure":
         fl_config(args, algo)  # rejected combinations fail here on either engine, before any data is loaded
     log_path = os.path.join(args.log_dir, args.dataset, args.identity + ".log")
     logger = logger_config(log_path=log_path, logging_name=args.identity)

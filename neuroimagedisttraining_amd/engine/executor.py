@@ -67,7 +67,7 @@ class FLConfig:
     prox_mu: float = 0.0          # FedProx proximal coefficient (0 = FedAvg/SalientGrads)
     group: int = 0                # max clients per lockstep launch (0 = all local clients)
     test_batch: int = 256
-    aggregator: str = "fedavg"    # fedavg | krum | multikrum | median | trimmed_mean (BASELINE config 4)
+    aggregator: str = "fedavg"    # fedavg | krum | multikrum | median | trimmed_mean (BASELINE config 4) | secure
     byzantine_f: int = 0          # Krum's assumed number of Byzantine clients
     multikrum_m: int = 0          # Multi-Krum: number of selected clients (0 = K - f)
     trim_ratio: float = 0.1       # trimmed mean: fraction cut from each end per coordinate
@@ -107,8 +107,24 @@ class FLConfig:
     defense_type: str = "none"    # none | norm_diff_clipping | weak_dp (clipping, then N(0, stddev^2) per client)
     norm_bound: float = 5.0       # L2 radius each client's update w_i - w_g (weight params only) is clipped to
     stddev: float = 0.025         # weak_dp noise scale
+    # ---- aggregator="secure": masked FedAvg over Z_p on the client rows (engine/secagg.py, csrc/kernels/secagg.hip)
+    secagg_scale: int = 2 ** 16   # fixed-point scale S of the quantised updates
+    secagg_dropout: float = 0.0   # fraction of the sampled clients that drop after the key setup (never upload)
+    secagg_threshold: int = 0     # BGW threshold T of the shared secret keys (0 = sampled clients per round // 2)
+    secagg_fuse: bool = True      # False: materialise every client's masked upload (the protocol's real cost)
 
     def __post_init__(self):
+        if self.aggregator == "secure":
+            # secure aggregation is FedAvg's weighted mean in Z_p: the defence (checked below) and the sparse top-k
+            # exchange would need the server to see individual updates
+            if self.update_topk > 0:
+                raise ValueError("aggregator=secure cannot be combined with update_topk=%s (only update_topk=0)"
+                                 % (self.update_topk,))
+            if not (1 <= int(self.secagg_scale) <= 2 ** 24 and 0.0 <= self.secagg_dropout < 1.0
+                    and self.secagg_threshold >= 0):
+                raise ValueError("aggregator=secure needs 1 <= secagg_scale <= 2^24, 0 <= secagg_dropout < 1 and "
+                                 "secagg_threshold >= 0 (got %s, %s, %s)"
+                                 % (self.secagg_scale, self.secagg_dropout, self.secagg_threshold))
         if self.defense_type not in ("none", "norm_diff_clipping", "weak_dp"):
             raise ValueError("defense_type %r: one of none | norm_diff_clipping | weak_dp" % (self.defense_type,))
         if self.defense_type != "none":

@@ -103,6 +103,44 @@ def _mix_hash_np(seed, a, b):
         return (z >> np.uint64(32)).astype(np.uint64)
 
 
+def _mix_hash64_np(seed, a, b):
+    """All 64 bits of the same finaliser (numpy twin of ``sec_mix64`` in secagg.hip); :func:`_mix_hash_np` is its
+    high half."""
+    with np.errstate(over="ignore"):
+        a = np.asarray(a, dtype=np.uint64)
+        b = np.asarray(b, dtype=np.uint64)
+        z = np.uint64(seed) ^ (np.uint64(0x9e3779b97f4a7c15) * ((a << np.uint64(32)) ^ b))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)
+        z ^= z >> np.uint64(31)
+        return z.astype(np.uint64)
+
+
+# ---- counter-based mask PRG of the secure aggregation: the one definition the HIP kernels (csrc/kernels/secagg.hip),
+# their numpy twins (engine/secagg.py) and the host trainer (algorithms/turboaggregate.py, prg="counter") share.  A
+# statistical PRG, as the reference's numpy streams are: this simulates the protocol's data flow and cost and makes no
+# cryptographic strength claim.
+MERSENNE31 = 2 ** 31 - 1
+
+
+def mod_mersenne31(z):
+    """``z mod (2^31 - 1)`` of uint64 ``z`` by Mersenne folding (2^31 = 1 mod p), all sums in 64 bits: exact for every
+    64-bit z (numpy twin of ``sec_modp``)."""
+    z = np.asarray(z, dtype=np.uint64)
+    m = np.uint64(MERSENNE31)
+    s = (z & m) + ((z >> np.uint64(31)) & m) + (z >> np.uint64(62))  # <= 2p + 3 = 2^32 + 1
+    s = (s & m) + (s >> np.uint64(31))                                # <= p + 2
+    return np.where(s >= m, s - m, s)
+
+
+def counter_mask(key, round_idx, seg, j):
+    """``m(key, round, seg, j) = z mod p``: ``z`` is every bit of :func:`_mix_hash64_np` over
+    ``seed = (round << 32) | key``, ``a = seg`` (0 = parameters, 1 = buffers), ``b = j``.  The round is part of the
+    seed, so a mask is never used twice.  int64 in [0, p)."""
+    seed = ((int(round_idx) & 0xffffffff) << 32) | (int(key) & 0xffffffff)
+    return mod_mersenne31(_mix_hash64_np(seed, int(seg), np.asarray(j, dtype=np.uint64))).astype(np.int64)
+
+
 def _keys_torch(mode, v, bit, seed, cid, idx):
     """Selection keys (int64, larger first, 0 = not a candidate) — the torch twin of ``sel_key``."""
     if mode == REGROW_RAND:

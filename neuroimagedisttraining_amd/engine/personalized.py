@@ -52,6 +52,9 @@ class PersonalizedRunner(FLRunner):
     """Shared machinery: personal rows, per-client mask bit rows, neighbour row exchange, local evaluations."""
 
     def __init__(self, engine, splits, cfg, info, template_model, logger=None, algorithm="local"):
+        if cfg.aggregator == "secure":  # these runners never form FedAvg's global mean, which is what gets masked
+            raise ValueError("aggregator=secure cannot be combined with algorithm=%s (only salientgrads / fedavg / "
+                             "fedprox)" % (algorithm,))
         if cfg.defense_type != "none":  # these runners never form FedAvg's global row sum the defence rides on
             raise ValueError("defense_type=%s cannot be combined with algorithm=%s (only salientgrads / fedavg / "
                              "fedprox)" % (cfg.defense_type, algorithm))

@@ -89,7 +89,7 @@ class StatInfo(dict):
     GPU loop never waits for a metric."""
 
     DEFERRED = ("global_test_acc", "global_test_loss", "person_test_acc", "person_test_loss", "test_acc",
-                "defense_clipped", "defense_max_ratio")
+                "defense_clipped", "defense_max_ratio", "secagg_saturated", "secagg_dropped")
 
     def __init__(self, flush, *a, **kw):
         super().__init__(*a, **kw)
@@ -919,6 +919,8 @@ class FLRunner:
     def aggregate(self, sampled):
         if self.cfg.defense_type != "none":
             return self.aggregate_defended(sampled)
+        if self.cfg.aggregator == "secure":
+            return self.aggregate_secure(sampled)
         if self.cfg.aggregator != "fedavg":
             return self.aggregate_robust(sampled)
         if self.cfg.update_topk > 0:
@@ -1107,6 +1109,49 @@ class FLRunner:
         dict.__setitem__(self.stat_info, "defense_clipped", int(round(float(r[0]))))
         dict.__setitem__(self.stat_info, "defense_max_ratio", float(r[1]))
         return dict(defense_clipped=int(round(float(r[0]))), defense_max_ratio=float(r[1]))
+
+    def aggregate_secure(self, sampled):
+        """FedAvg's weighted mean as a secure aggregation over Z_p, p = 2^31 - 1 (``engine/secagg.py``,
+        ``csrc/kernels/secagg.hip``; the eager oracle is ``TurboAggregateTrainer(prg="counter")``).
+
+        Every sampled client quantises its weighted row to fixed point (scale ``cfg.secagg_scale``) and masks it with
+        one counter-based stream per peer, keyed by the pair's agreed key and the round; the server sums mod p,
+        removes the masks towards the clients that dropped after the key setup (``cfg.secagg_dropout`` of the sampled
+        ones, drawn from (cfg.seed, round); their secret keys come back from the survivors' BGW shares, threshold
+        ``cfg.secagg_threshold``) and de-quantises.  BN buffers take the same path as a second segment.
+
+        One rank: ``secagg_masked_sum`` over the rows in place, then ``secagg_finish``.  Several ranks: one int64 SUM
+        all-reduce of the partials in between.  The arithmetic is integer arithmetic, so the result is bit-identical
+        for any sharding.  ``cfg.secagg_fuse = False`` materialises every client's masked upload in row chunks and
+        sums them: the protocol's real cost, the same bits.
+
+        The all-reduce is dense, also under a SalientGrads mask: a rank's partial is uniform in Z_p at every
+        coordinate, pruned or not, until the other ranks' masks cancel it.  Compacting the exchange (masks only on the
+        kept coordinates) is out of scope here.
+
+        ``stat_info["secagg_saturated"]`` (values that hit the fixed-point bound or were not finite, all ranks) and
+        ``["secagg_dropped"]`` stay on the device and are read where the deferred metrics are: no host sync here."""
+        from . import secagg as SA
+        cfg = self.cfg
+        K = len(sampled)
+        T = int(cfg.secagg_threshold) or SA.default_threshold(K)
+        if getattr(self, "_secagg_keys", None) is None or self._secagg_keys.T != T:
+            self._secagg_keys = SA.SecAggKeys(self.N, T, seed=cfg.seed, scale=cfg.secagg_scale)
+        round_idx = getattr(self, "_round_idx", 0)
+        dropped = SA.draw_dropped(cfg.seed, round_idx, sampled, cfg.secagg_dropout, T)
+        rows, loc = self._local_rows(sampled)
+        st = SA.aggregate(self.theta, self.bufs, self.P, self.Q, rows, loc, sampled, self.sizes, self.info,
+                          self._secagg_keys, round_idx, self.w_global, self.b_global, scale=cfg.secagg_scale,
+                          dropped=dropped, fuse=bool(cfg.secagg_fuse),
+                          hip=self.device.type == "cuda")  # a CUDA device without the extension is an error
+        self.stat_info["aggregate_elems"] = int(self.P + self.Q)
+        self._defer_result(round_idx, st.double(), recorder=self._record_secagg)
+
+    def _record_secagg(self, round_idx, r):
+        res = dict(secagg_saturated=int(round(float(r[0]))), secagg_dropped=int(round(float(r[1]))))
+        for k, v in res.items():
+            dict.__setitem__(self.stat_info, k, v)
+        return res
 
     def aggregate_robust(self, sampled):
         """Byzantine-robust aggregation (BASELINE config 4): Krum / Multi-Krum / coordinate median / trimmed mean
