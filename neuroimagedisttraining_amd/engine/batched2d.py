@@ -96,9 +96,9 @@ class BatchedModuleEngine:
         self._shift = (-torch.tensor(mean, dtype=torch.float32, device=self.device)
                        / torch.tensor(std, dtype=torch.float32, device=self.device)).view(1, c, 1, 1)
         self._opt = None
-        # GPU: the hand-written grouped layers (conv2d_hip.py: conv2d_any.hip convolutions, batched GEMM linears,
-        # grouped GroupNorm) over group-stacked tensors instead of vmapped library convolutions; NIDT_B2D_HIP=0 keeps
-        # the vmap path (the CPU always uses it)
+        # GPU: the hand-written grouped layers (conv2d_hip.py: conv2d_any.hip convolutions, linear_g.hip linears on
+        # the fp32 rows in place, grouped GroupNorm) over group-stacked tensors instead of vmapped library calls;
+        # NIDT_B2D_HIP=0 keeps the vmap path (the CPU always uses it)
         self._grouped = None
         if self.device.type == "cuda" and os.environ.get("NIDT_B2D_HIP", "1") != "0":
             from . import conv2d_hip

@@ -1,4 +1,5 @@
-"""Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_any.hip``).
+"""Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_any.hip``,
+``linear_g.hip``).
 
 The small models of the reference's entry points (``lenet5``, ``cnn_cifar10/100``, the EMNIST CNNs, ``vgg11/16`` —
 ``fedml_experiments/standalone/subavg/main_subavg.py:143-158``) run G clients of a lockstep step as one pass over
@@ -8,7 +9,10 @@ modules are replaced by grouped twins reading the clients' parameter rows (``[G,
 * ``Conv2d`` (stride 1, any kernel size and channel count) -> :class:`HipConv2dFn`: forward and stride-1 data
   gradient on the implicit-GEMM MFMA kernel, weight gradient on the staged fp32 kernel (``conv2d_any.hip``); the
   activations stay channels-last (``torch.channels_last`` views), bf16;
-* ``Linear`` -> one batched GEMM per layer (``baddbmm`` over the client axis);
+* ``Linear`` -> :class:`HipLinearFn`: forward, data gradient and weight / bias gradient on the MFMA kernels of
+  ``linear_g.hip``, which read the fp32 weight rows in place (rounded to bf16 in registers, no bf16 weight copy) and
+  write fp32-accumulated fp32 weight gradients in a fixed order; ``NIDT_B2D_LINEAR=0`` (and the CPU) keeps one
+  batched library GEMM per layer (``baddbmm`` over the client axis);
 * ``GroupNorm`` -> ``group_norm`` without affine on the stacked batch, then the per-client affine;
 * everything else (ReLU, max-pool, dropout, flatten) is per-sample and runs unchanged on the stacked batch.
 
@@ -17,6 +21,7 @@ The model's own ``forward`` runs as written, so the layer order and every view/f
 from __future__ import annotations
 
 import copy
+import os
 
 import torch
 import torch.nn as nn
@@ -103,6 +108,60 @@ class HipConv2dFn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+def _rows_bf16(x):
+    return x.detach().to(torch.bfloat16).contiguous()
+
+
+class HipLinearFn(torch.autograd.Function):
+    """Grouped Linear on ``linear_g.hip``: x [G*B, K] (any float dtype), w the [G, N, K] fp32 view of the clients'
+    rows (strides (ld, K, 1), read in place: no bf16 copy of the weights is made), b [G, N] (strides (ld, 1)) or
+    None.  Returns bf16 [G*B, N]; the backward gives bf16 dx and fp32-accumulated fp32 dw / db."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, G):
+        m = ops.ext()
+        M, K = x.shape
+        N = w.shape[1]
+        assert M % G == 0 and w.shape[0] == G and w.shape[2] == K and w.dtype == torch.float32
+        ldw = w.stride(0)
+        assert w.stride() == (ldw, K, 1), "HipLinearFn: w must be a [G, N, K] view of the clients' rows"
+        ldb = 0
+        if b is not None:
+            ldb = b.stride(0)
+            assert b.shape == (G, N) and b.stride() == (ldb, 1) and b.dtype == torch.float32
+        xs = _rows_bf16(x)
+        y = torch.empty(M, N, device=x.device, dtype=torch.bfloat16)
+        m.linear_g_fwd(xs.data_ptr(), w.data_ptr(), ldw, b.data_ptr() if b is not None else 0, ldb, y.data_ptr(), G,
+                       M // G, K, N, _stream())
+        ctx.save_for_backward(xs, w)
+        ctx.G, ctx.has_b = G, b is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        m = ops.ext()
+        xs, w = ctx.saved_tensors
+        G = ctx.G
+        M, K = xs.shape
+        N, B = w.shape[1], M // G
+        dy = _rows_bf16(gy)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(M, K, device=xs.device, dtype=torch.bfloat16)
+            m.linear_g_dgrad(dy.data_ptr(), w.data_ptr(), w.stride(0), dx.data_ptr(), G, B, K, N, _stream())
+        if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
+            dw = torch.empty(G, N, K, device=xs.device, dtype=torch.float32)
+            if ctx.has_b:
+                db = torch.empty(G, N, device=xs.device, dtype=torch.float32)
+            m.linear_g_wgrad(xs.data_ptr(), dy.data_ptr(), dw.data_ptr(), N * K, db.data_ptr() if ctx.has_b else 0, N,
+                             G, B, K, N, _stream())
+        return dx, dw, db, None
+
+
+def _hip_linear_on():
+    return os.environ.get("NIDT_B2D_LINEAR", "1") != "0"
+
+
 class _Group:
     """The current step's grouping: G and the per-client parameter views {name: [G, *shape]}."""
 
@@ -140,6 +199,8 @@ class GLinear(nn.Module):
     def forward(self, x):
         G, P = self.grp.G, self.grp.params
         w = P[self.name + ".weight"]
+        if x.is_cuda and _hip_linear_on():
+            return HipLinearFn.apply(x, w, P[self.name + ".bias"] if self.has_b else None, G)
         xg = x.reshape(G, x.shape[0] // G, x.shape[1])
         if not torch.is_autocast_enabled():
             xg = xg.to(w.dtype)
