@@ -9,9 +9,12 @@
 //    16x16x32 bf16 MFMA, block = 4 waves = 64 positions x 64 output channels, wave = 32 x 32.  K = kt x Cinp
 //    (Cinp = Cin rounded up to 8) walks 32 at a time; a lane's 8 consecutive k are 8 channels of one tap: one 16-B load
 //    when the channel stride allows it, element loads otherwise (first layers); out-of-image taps read zeros;
-//  * weight gradient: per (client, tap, 64 x 64 channel tile, 256-position chunk) block, dY and the tap-shifted X rows
-//    staged through LDS as fp32, 4 x 4 register micro-tiles of fp32 FMAs, one deterministic fp32 partial per chunk
-//    (the host sums the chunks in a fixed order).
+//  * weight gradient (k_conv2d_any_wgrad): the staged fp32 kernel that conv2d_wg.hip's MFMA kernel replaced as the
+//    default; kept as the A/B side (NIDT_B2D_WGRAD=0), for kernels above 7 x 7 and for launches too small to fill
+//    the GPU with one block per output tile (conv2d_hip.py conv2d_wg_ok, profiles/r11_conv2d_wgrad.txt).  Per
+//    (client, tap, 64 x 64 channel tile, 256-position chunk) block, dY and the tap-shifted X rows staged through LDS
+//    as fp32, 4 x 4 register micro-tiles of fp32 FMAs, one deterministic fp32 partial per chunk (the host sums the
+//    chunks in a fixed order).
 #include "common.h"
 
 namespace nidt {

@@ -1,5 +1,5 @@
 """Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_any.hip``,
-``linear_g.hip``).
+``conv2d_wg.hip``, ``linear_g.hip``).
 
 The small models of the reference's entry points (``lenet5``, ``cnn_cifar10/100``, the EMNIST CNNs, ``vgg11/16`` —
 ``fedml_experiments/standalone/subavg/main_subavg.py:143-158``) run G clients of a lockstep step as one pass over
@@ -7,8 +7,11 @@ group-stacked tensors ``[G*B, C, H, W]``: a deep copy of the model whose ``Conv2
 modules are replaced by grouped twins reading the clients' parameter rows (``[G, *shape]`` views of theta):
 
 * ``Conv2d`` (stride 1, any kernel size and channel count) -> :class:`HipConv2dFn`: forward and stride-1 data
-  gradient on the implicit-GEMM MFMA kernel, weight gradient on the staged fp32 kernel (``conv2d_any.hip``); the
-  activations stay channels-last (``torch.channels_last`` views), bf16;
+  gradient on the implicit-GEMM MFMA kernel (``conv2d_any.hip``), weight and bias gradient on the MFMA kernel of
+  ``conv2d_wg.hip``, which owns each output element and writes fp32 in the parameter layout, both bf16 weight images
+  from one ``conv2d_pack_w`` launch; ``NIDT_B2D_WGRAD=0`` keeps the staged fp32 weight-gradient kernel of
+  ``conv2d_any.hip`` with its framework partial sum, bias sum and packing; the activations stay channels-last
+  (``torch.channels_last`` views), bf16;
 * ``Linear`` -> :class:`HipLinearFn`: forward, data gradient and weight / bias gradient on the MFMA kernels of
   ``linear_g.hip``, which read the fp32 weight rows in place (rounded to bf16 in registers, no bf16 weight copy) and
   write fp32-accumulated fp32 weight gradients in a fixed order; ``NIDT_B2D_LINEAR=0`` (and the CPU) keeps one
@@ -59,8 +62,63 @@ def pack_conv_wt(w):
     return img.to(torch.bfloat16).contiguous()
 
 
+def _hip_wgrad_on():
+    return os.environ.get("NIDT_B2D_WGRAD", "1") != "0"
+
+
+WG_MIN_BLOCKS = 64
+
+
+def conv2d_wg_lds_bytes(k, Wo, cin):
+    """The dynamic LDS of a ``conv2d_wg`` launch: the launcher's own arithmetic (two buffers of a 32 x 72 dY tile and
+    of ``nu`` union rows of ci tile + 8 bf16 elements, nu = 32 + (k - 1) min(32, 1 + ceil(31 / Wo)))."""
+    nu = 32 + (k - 1) * min(32, 1 + (31 + Wo - 1) // Wo)
+    return 2 * 2 * (32 * 72 + nu * ((16 if cin <= 16 else 64) + 8))
+
+
+def conv2d_wg_ok(k, Wo, G, cin, cout):
+    """The layers whose weight gradient runs on ``conv2d_wg``; everything else keeps ``conv2d_any_wgrad``.
+
+    * the launcher's rule: kernels up to 7 x 7 whose LDS tiles fit 64 KiB (of those only a 7 x 7 kernel with more
+      than 16 input channels on a 1-wide output map does not: 73 728 B);
+    * the measured rule (``profiles/r11_conv2d_wgrad.txt``): one block owns each output element and walks the whole
+      contraction, so a launch of fewer than ``WG_MIN_BLOCKS`` blocks (clients x ci tiles x co tiles x k) is
+      latency-bound.  At 8 clients x 64 images the 24- to 48-block launches ran at 0.49x - 0.99x of the parent path
+      on five layers (1.13x - 1.40x on three others, which this rule gives up); the smallest launch measured above
+      48 blocks had 192 (3.2x), and every launch of 192 blocks or more was 3.2x - 11x faster.  The threshold of 64 is
+      interpolated between 48 (0.99x) and 192: no launch of 49 .. 191 blocks was measured.  The rule looks at the
+      block count alone, not at the contraction length B Ho Wo, the other half of "latency-bound": among the 40-block
+      launches 128 steps ran at 0.80x, 200 steps at 1.24x - 1.40x and 1568 steps at 0.86x and at 1.13x, so the
+      measurements give no length threshold."""
+    blocks = G * (1 if cin <= 16 else (cin + 63) // 64) * ((cout + 63) // 64) * k
+    return k <= 7 and conv2d_wg_lds_bytes(k, Wo, cin) <= 65536 and blocks >= WG_MIN_BLOCKS
+
+
+def _client_blocks(w):
+    """w [G, ...] as (tensor whose clients are contiguous blocks at one stride, that stride in elements)."""
+    if not (w.dtype == torch.float32 and w[0].is_contiguous() and (w.shape[0] == 1 or w.stride(0) >= w[0].numel())):
+        w = w.float().contiguous()
+    return w, (w.stride(0) if w.shape[0] > 1 else w[0].numel())
+
+
+def pack_conv_images(w, transposed):
+    """``pack_conv_w(w)`` and, if asked for, ``pack_conv_wt(w)`` (else None) by one ``conv2d_pack_w`` launch that
+    reads the clients' fp32 blocks where they lie."""
+    G, co, ci, k, _ = w.shape
+    w, ldw = _client_blocks(w)
+    wp = torch.empty(G, (co + 63) // 64 * 64, k * k, (ci + 7) // 8 * 8, device=w.device, dtype=torch.bfloat16)
+    wt = torch.empty(G, (ci + 63) // 64 * 64, k * k, (co + 7) // 8 * 8, device=w.device,
+                     dtype=torch.bfloat16) if transposed else None
+    ops.ext().conv2d_pack_w(w.data_ptr(), ldw, wp.data_ptr(), wt.data_ptr() if transposed else 0, G, co, ci, k,
+                            _stream())
+    return wp, wt
+
+
 class HipConv2dFn(torch.autograd.Function):
-    """Grouped stride-1 conv: x [G*B, Cin, H, W] (any strides), w [G, Cout, Cin, k, k] fp32, b [G, Cout] or None."""
+    """Grouped stride-1 conv: x [G*B, Cin, H, W] (any strides), w [G, Cout, Cin, k, k] fp32, b [G, Cout] or None.
+    With ``NIDT_B2D_WGRAD=1`` (the default) the weight images come from ``conv2d_pack_w`` and the weight / bias
+    gradients from ``conv2d_wg`` (``conv2d_wg.hip``), in the parameter layout; 0 keeps the framework packing and
+    ``conv2d_any_wgrad`` with its partial sums."""
 
     @staticmethod
     def forward(ctx, x, w, b, G, pad):
@@ -72,18 +130,23 @@ class HipConv2dFn(torch.autograd.Function):
         xs = _nhwc_bf16(x)
         Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
         y = torch.empty(N, Ho, Wo, co, device=x.device, dtype=torch.bfloat16)
-        wp = pack_conv_w(w.detach())
+        ctx.new = _hip_wgrad_on()
+        wt = None
+        if ctx.new:
+            wp, wt = pack_conv_images(w.detach(), ctx.needs_input_grad[0])
+        else:
+            wp = pack_conv_w(w.detach())
         bias = b.detach().float().contiguous() if b is not None else None
         m.conv2d_any_fwd(xs.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else 0, y.data_ptr(), G, B,
                          H, W, ci, ci, co, k, pad, _stream())
-        ctx.save_for_backward(xs, w)
+        ctx.save_for_backward(xs, w, wt)
         ctx.G, ctx.pad, ctx.has_b = G, pad, b is not None
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
         m = ops.ext()
-        xs, w = ctx.saved_tensors
+        xs, w, wt = ctx.saved_tensors
         G, pad = ctx.G, ctx.pad
         N, H, W, ci = xs.shape
         co, k = w.shape[1], w.shape[3]
@@ -92,18 +155,30 @@ class HipConv2dFn(torch.autograd.Function):
         Ho, Wo = dy.shape[1], dy.shape[2]
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            wt = pack_conv_wt(w.detach())
+            if wt is None:
+                wt = pack_conv_wt(w.detach())
             dxs = torch.empty(N, H, W, ci, device=xs.device, dtype=torch.bfloat16)
             m.conv2d_any_fwd(dy.data_ptr(), wt.data_ptr(), 0, dxs.data_ptr(), G, B, Ho, Wo, co, co, ci, k, k - 1 - pad,
                              _stream())
             dx = dxs.permute(0, 3, 1, 2)
+        want_b = ctx.has_b and ctx.needs_input_grad[2]
+        if ctx.new and conv2d_wg_ok(k, Wo, G, ci, co):
+            if ctx.needs_input_grad[1] or want_b:
+                # dB comes from the dY tiles that the dW blocks stage: the kernel cannot skip dW, so a bias-only
+                # gradient (no layer of the zoo asks for one) still computes and returns the whole dw
+                dw = torch.empty(G, co, ci, k, k, device=xs.device, dtype=torch.float32)
+                if want_b:
+                    db = torch.empty(G, co, device=xs.device, dtype=torch.float32)
+                m.conv2d_wg(xs.data_ptr(), dy.data_ptr(), dw.data_ptr(), co * ci * k * k,
+                            db.data_ptr() if want_b else 0, co, G, B, H, W, ci, ci, co, k, pad, _stream())
+            return dx, dw, db, None, None
         if ctx.needs_input_grad[1]:
             nch = m.conv2d_any_wgrad_chunks(B, Ho, Wo)
             part = torch.empty(nch, G, co, k * k, ci, device=xs.device, dtype=torch.float32)
             m.conv2d_any_wgrad(xs.data_ptr(), dy.data_ptr(), part.data_ptr(), G, B, H, W, ci, ci, co, k, pad,
                                _stream())
             dw = part.sum(0).view(G, co, k, k, ci).permute(0, 1, 4, 2, 3).contiguous()
-        if ctx.has_b and ctx.needs_input_grad[2]:
+        if want_b:
             db = dy.float().view(G, B * Ho * Wo, co).sum(1)
         return dx, dw, db, None, None
 
