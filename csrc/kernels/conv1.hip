@@ -5,7 +5,7 @@
 //  * Input volumes live in HBM as uint8 in a *polyphase* layout [N][61][73][61][8]: voxel (d,h,w) is stored at
 //    (d>>1, h>>1, w>>1) phase ((d&1)<<2 | (h&1)<<1 | (w&1)).  The stride-2 5^3 conv becomes a stride-1 3^3 conv
 //    over 8 "phase channels": every MFMA B fragment (8 consecutive k = the 8 phases of one tap) is one 16-B
-//    contiguous read.  K = 27 taps x 8 phases = 216 (125 live), padded to 224 = 7 k-steps of 32.
+//    contiguous read.  K = 27 taps x 8 phases = 216 (125 live), packed into 128 slots = 4 k-steps of 32.
 //    uint8 values are exact in bf16, so B = u8 and A = bf16(w/255): conv == sum w * (u8/255).
 //  * BatchNorm batch statistics need no pass over the 253 M-element conv output: with per-sample patch moments
 //    m1 = sum_pos p, m2 = sum_pos p p^T (computed once when the data is loaded; exact int-valued fp64),
@@ -20,7 +20,6 @@
 #include <type_traits>
 
 #include "common.h"
-#include "conv1_wgrad_layout.h"
 #include "conv1_mx_layout.h"
 
 namespace nidt {
@@ -29,7 +28,7 @@ constexpr int kPZ = 61, kPY = 73, kPX = 61;          // polyphase grid of a 121x
 constexpr int kOD = 59, kOH = 71, kOW = 59;          // conv1 output
 constexpr int kPD = 19, kPH = 23, kPW = 19;          // pooled output
 constexpr int kC1 = 64;
-constexpr int kK1 = 224;                              // padded k (27 taps x 8 phases = 216)
+constexpr int kK1 = 128;                              // packed K slots of the forward (125 live)
 constexpr int kNM = 125 + 125 * 125;                  // per-sample moment vector length
 
 // phase r = (rd<<2)|(rh<<1)|rw ; tap t = jd*9+jh*3+jw ; original k = kd*25+kh*5+kw with kd = 2 jd + rd
@@ -160,46 +159,30 @@ void conv1_sample_moments(uintptr_t x8, int64_t N, uintptr_t mom, uintptr_t stre
 // 8 bytes) + H[fq] (phases 0,1,4,5: dwords 0 and 2); k-step 3 = W[fq] (phases 0,2,4,6: the low halves of the 4
 // dwords, two v_perm) + two 2-phase groups (or DHW) picked by one v_cndmask + v_perm each.  Only 3 of 128 slots are
 // empty (vs 99 of 224 in the 27 x 8 layout).
-// [RO]: RO = 1 orders the groups of k-steps 0-2 so that the two lane quarters of each ds_read_b128 lane group (fq 0
-// with 1, fq 2 with 3) read tap groups of the same jw (their halo offsets then differ by whole 1-KB (dd, dh) rows:
-// the same banks for the same column, no conflict); RO = 0 is the original order and the
-// default (RO = 1 measured slower, NIDT_C1_TAPORD=1 for A/B)
-__device__ constexpr int kC1F2[2][8] = {{0, 1, 3, 4, 9, 10, 12, 13}, {0, 3, 1, 4, 9, 12, 10, 13}};
-__device__ constexpr int kC1D2[2][4] = {{18, 19, 21, 22}, {18, 21, 19, 22}};
-__device__ constexpr int kC1H2[2][4] = {{6, 7, 15, 16}, {6, 15, 7, 16}};
+// Two other tap-group orders were measured and dropped: groups paired by jw for the ds_read_b128 lane groups ran
+// slower (conv1 forward 4.38 vs 4.25 ms at 64 clients, profiles/r4_kbench_g64.txt); an all-b128 layout took the
+// LDS bank conflicts from 45.7 % to 0.0 % with the time unchanged (3.28 ms either way, profiles/r6_conv1_b128.txt:
+// the conflicts are not what the kernel waits on) and other fp32 rounding (another k order).
+__device__ constexpr int kC1F[8] = {0, 1, 3, 4, 9, 10, 12, 13};
+__device__ constexpr int kC1D[4] = {18, 19, 21, 22};
+__device__ constexpr int kC1H[4] = {6, 7, 15, 16};
 __device__ constexpr int kC1W[4] = {2, 5, 11, 14};
 __device__ constexpr int kC1X1[4] = {24, 20, 8, 26};   // DH0, DW0, HW0, DHW
 __device__ constexpr int kC1X2[4] = {25, 23, 17, 26};  // DH1, DW1, HW1, (empty)
 __device__ constexpr int kC1XR[4][2] = {{0, 1}, {0, 2}, {0, 4}, {0, -1}};
-// RO = 2 (opt-in, NIDT_C1_TAPORD=2): every B operand is one conflict-free ds_read_b128.  A ds_read_b128 is served in 16-lane
-// groups {fq0 fr0-3,12-15 + fq1 fr4-11} (and the fq2/fq3 mirror): when the two lane quarters of a group read tap
-// groups of the same jw, their 16 lanes touch 16 distinct 16-B slots of the 256-B bank row.  k-steps 0-2 take the
-// RO = 1 order (paired jw); k-step 3 holds W[fq] (phases 0,2,4,6) + X1[fq] (phases 0,2: DW0, DW1, DHW, empty) +
-// X2[fq] (phases 0,1 for DH0/DH1, 0,4 for HW0/HW1).  Only X2 of the fq0/fq1 quarters (DH0: jw 0 vs DH1: jw 1) is
-// 2-way.  The narrow reads of RO = 0/1 (ds_read_b64 / b32 at a 16-B lane stride: 2- and 4-way) were the kernel's
-// 45.7 % LDS bank conflicts (profiles/r5_c1fwd_w64_pmc.txt).
-__device__ constexpr int kC1X1b[4] = {20, 23, 26, -1};  // DW0, DW1, DHW, empty
-__device__ constexpr int kC1X2b[4] = {24, 25, 8, 17};   // DH0, DH1, HW0, HW1
 
 // (tap group, phase) of slot kk of the 128-slot layout, or t = -1 for an empty slot
-template <int RO>
 __device__ __forceinline__ void c1_slot128(int kk, int& t, int& r) {
-  constexpr int R1 = RO ? 1 : 0;
   const int st = kk >> 5, fq = (kk >> 3) & 3, e = kk & 7;
   t = -1;
   r = 0;
-  if (st < 2) { t = kC1F2[R1][4 * st + fq]; r = e; return; }
+  if (st < 2) { t = kC1F[4 * st + fq]; r = e; return; }
   if (st == 2) {
-    if (e < 4) { t = kC1D2[R1][fq]; r = e; }
-    else { t = kC1H2[R1][fq]; r = (e - 4 < 2) ? e - 4 : e - 4 + 2; }
+    if (e < 4) { t = kC1D[fq]; r = e; }
+    else { t = kC1H[fq]; r = (e - 4 < 2) ? e - 4 : e - 4 + 2; }
     return;
   }
   if (e < 4) { t = kC1W[fq]; r = 2 * e; return; }
-  if (RO == 2) {
-    if (e < 6) { t = kC1X1b[fq]; r = e == 4 ? 0 : 2; }  // DHW's phase 2 is invalid: tp_valid zeroes its weight
-    else { t = kC1X2b[fq]; r = e == 6 ? 0 : (fq < 2 ? 1 : 4); }
-    return;
-  }
   const int x = (e - 4) >> 1, h = e & 1;
   if (x == 1 && fq == 3) return;
   const int rr = kC1XR[fq][h];
@@ -208,25 +191,18 @@ __device__ __forceinline__ void c1_slot128(int kk, int& t, int& r) {
   r = rr;
 }
 
-// weight packing: theta row g at off: [64][125] fp32 -> w8 [G][64][KS] f16 bits of f16(w) (the forward's MFMA
-// A operand, against raw uint8 voxels; KS = 128 slots, or 224 = 27 x 8 for the legacy layout), w125 [G][64][125]
-// f32 = f16(w) * scale (scale = 1/255): the exact effective weights of conv(x / 255) that the moment math (BN
-// statistics) and the closed-form backward use.
-template <int RO>
+// weight packing: theta row g at off: [64][125] fp32 -> w8 [G][64][128] f16 bits of f16(w) (the forward's MFMA
+// A operand, against raw uint8 voxels), w125 [G][64][125] f32 = f16(w) * scale (scale = 1/255): the exact effective
+// weights of conv(x / 255) that the moment math (BN statistics) and the closed-form backward use.
 __global__ void k_pack_conv1_w(const float* __restrict__ theta, int64_t ldt, int64_t off, int64_t off_sign, int G,
-                               float scale, int KS, uint16_t* __restrict__ w8, float* __restrict__ w125) {
+                               float scale, uint16_t* __restrict__ w8, float* __restrict__ w125) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= G * kC1 * KS) return;
-  const int g = i / (kC1 * KS), rem = i - g * kC1 * KS, c = rem / KS, kk = rem - c * KS;
+  if (i >= G * kC1 * kK1) return;
+  const int g = i / (kC1 * kK1), rem = i - g * kC1 * kK1, c = rem / kK1, kk = rem - c * kK1;
   int t, r;
-  if (KS == 128) {
-    c1_slot128<RO>(kk, t, r);
-  } else {
-    t = kk >> 3;
-    r = kk & 7;
-  }
+  c1_slot128(kk, t, r);
   uint16_t v = 0;
-  if (t >= 0 && t < 27 && tp_valid(t, r)) {
+  if (t >= 0 && tp_valid(t, r)) {
     const int k = tp_to_k(t, r);
     const _Float16 h = (_Float16)theta[(int64_t)g * ldt + off + c * 125 + k];
     v = __builtin_bit_cast(uint16_t, h);
@@ -237,41 +213,14 @@ __global__ void k_pack_conv1_w(const float* __restrict__ theta, int64_t ldt, int
   w8[i] = v;
 }
 
-// K slots of the forward's packed weights: 128 (default) or the legacy 27 x 8 = 224 (NIDT_C1_K224=1, A/B)
-// tap-group order of the 128-slot forward layout (pack and forward must agree): the original order by default;
-// NIDT_C1_TAPORD=1 selects the bank-paired order (slower at 64 clients: conv1 forward 4.38 vs 4.25 ms,
-// profiles/r4_kbench_g64.txt)
-// NIDT_C1_TAPORD=2 (A/B, the w64 forward only): the all-b128 layout [RO = 2]: LDS bank conflicts 45.7 % -> 0.0 %
-// with the forward's time unchanged (3.28 ms per 64-client step either way, profiles/r6_conv1_b128.txt) — the
-// conflicts are not what the kernel waits on.  Its fp32 sums differ from RO = 0 by rounding (another k order), which
-// flips near-tie max-pool / ReLU decisions downstream; RO = 0 stays the default.  The pipe kernel knows RO 0 / 1.
-int conv1_kslots();
-int conv1_fwd_variant();
-int conv1_tapord() {
-  static const int env = env_int("NIDT_C1_TAPORD", 0);
-  if (conv1_fwd_variant() == 1 && conv1_kslots() == 128) return env >= 0 && env <= 2 ? env : 0;
-  return env == 1 ? 1 : 0;
-}
-
-int conv1_kslots() {
-  static const int ks = env_int("NIDT_C1_K224", 0) == 1 ? kK1 : 128;
-  return ks;
-}
+// K slots of a packed weight row: the tests size their w8 buffers from it
+int conv1_kslots() { return kK1; }
 
 void pack_conv1_w(uintptr_t theta, int64_t ldt, int64_t off, int64_t off_sign, int G, float scale, uintptr_t w8,
                   uintptr_t w125, uintptr_t stream) {
-  const int KS = conv1_kslots();
-  // w125 entries of empty taps are never read; every valid (t, r) appears in exactly one slot of either layout
-  const int ro = conv1_tapord();
-  if (ro == 2)
-    hipLaunchKernelGGL(k_pack_conv1_w<2>, dim3(ceil_div(G * kC1 * KS, 256)), dim3(256), 0, as_stream(stream),
-                       ptr<const float>(theta), ldt, off, off_sign, G, scale, KS, ptr<uint16_t>(w8), ptr<float>(w125));
-  else if (ro == 1)
-    hipLaunchKernelGGL(k_pack_conv1_w<1>, dim3(ceil_div(G * kC1 * KS, 256)), dim3(256), 0, as_stream(stream),
-                       ptr<const float>(theta), ldt, off, off_sign, G, scale, KS, ptr<uint16_t>(w8), ptr<float>(w125));
-  else
-    hipLaunchKernelGGL(k_pack_conv1_w<0>, dim3(ceil_div(G * kC1 * KS, 256)), dim3(256), 0, as_stream(stream),
-                       ptr<const float>(theta), ldt, off, off_sign, G, scale, KS, ptr<uint16_t>(w8), ptr<float>(w125));
+  // w125 entries of empty taps are never read; every valid (t, r) appears in exactly one slot of the layout
+  hipLaunchKernelGGL(k_pack_conv1_w, dim3(ceil_div(G * kC1 * kK1, 256)), dim3(256), 0, as_stream(stream),
+                     ptr<const float>(theta), ldt, off, off_sign, G, scale, ptr<uint16_t>(w8), ptr<float>(w125));
   NIDT_CHECK(hipGetLastError());
 }
 
@@ -421,14 +370,12 @@ __device__ __forceinline__ float vmax3(float a, float b, float c) {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-// B fragment of k-step s (of KS per (dd, dh) row) for one output column: the lane's 8 consecutive k of the packed
-// layout read from the f16 halo at row offset ro.  KS = 7: tap group 4 s + fq, one 16-B read.  KS = 4: the
-// 128-slot layout of c1_slot128 (ga/gh/gx1/gx2: the lane's group offsets; xsrc2: lane picks dword 2 instead of 1
-// of its 2-phase groups; xsel1/xsel2: v_perm selectors of those groups).
-template <int KS>
+// B fragment of k-step s (of 4 per (dd, dh) row) for one output column: the lane's 8 consecutive k of the 128-slot
+// layout of c1_slot128 read from the f16 halo at row offset ro (ga/gh/gx1/gx2: the lane's group offsets; xsrc2: lane
+// picks dword 2 instead of 1 of its 2-phase groups; xsel1/xsel2: v_perm selectors of those groups).
 __device__ __forceinline__ f16x8 c1_bfrag(const uint16_t* hb, int s, int ro, const int* ga, int gh, int gx1, int gx2,
                                           bool xsrc2, uint32_t xsel1, uint32_t xsel2) {
-  if (KS == 7 || s < 2) return *reinterpret_cast<const f16x8*>(&hb[ro + ga[s]]);
+  if (s < 2) return *reinterpret_cast<const f16x8*>(&hb[ro + ga[s]]);
   if (s == 2) {
     const uint2 d = *reinterpret_cast<const uint2*>(&hb[ro + ga[2]]);  // D: phases 0-3
     const uint32_t h0 = *reinterpret_cast<const uint32_t*>(&hb[ro + gh]);      // H: phases 0,1
@@ -447,16 +394,17 @@ __device__ __forceinline__ f16x8 c1_bfrag(const uint16_t* hb, int s, int ro, con
   return __builtin_bit_cast(f16x8, v);
 }
 
-// PF: B-fragment prefetch distance in k-steps; KS: k-steps per (dd, dh) row (7 or 4); OCC: blocks per CU the
-// register budget is cut for (2: 256 VGPRs; 3: 168, with spills — A/B NIDT_C1_OCC)
-template <int PF, int KS, int OCC = 2, int DDU = 1, int RO = 1>
-__global__ __launch_bounds__(256, OCC) void k_conv1_fwd_pool_pipe(const uint8_t* __restrict__ x8,
+// Two blocks per CU (256 VGPRs; a budget cut for three spilled: 5.66 vs 4.31 ms per 64-client step,
+// profiles/r3_ab_conv1_fwd_occupancy.txt).  nq: row ranges per slab, always launched as 1.
+__global__ __launch_bounds__(256, 2) void k_conv1_fwd_pool_pipe(const uint8_t* __restrict__ x8,
                                                                 const int* __restrict__ idx,
                                                                 const uint16_t* __restrict__ w8,
                                                                 const float* __restrict__ scale,
                                                                 const float* __restrict__ shift, int B,
                                                                 uint16_t* __restrict__ out, uint8_t* __restrict__ amax,
                                                                 int nq) {
+  constexpr int PF = 2;  // B-fragment prefetch distance in k-steps
+  constexpr int KS = 4;  // k-steps per (dd, dh) row
   constexpr int HX = 64;
   constexpr int HALO = 5 * 5 * HX * 8;  // f16 elements per buffer
   constexpr int NLD = (5 * 5 * HX + 255) / 256;  // 7 halo voxels per thread
@@ -533,28 +481,16 @@ __global__ __launch_bounds__(256, OCC) void k_conv1_fwd_pool_pipe(const uint8_t*
   // halo offsets of this lane's tap groups (relative to the (dd, dh) row and the output column)
   auto goff = [](int t) { return (((t / 9) * 5 + (t / 3) % 3) * HX + (t % 3)) * 8; };
   int toff[KS];
-  int gh = 0, gx1 = 0, gx2 = 0;
-  bool xsrc2 = false;
-  uint32_t xsel1 = 0, xsel2 = 0;
-  if (KS == 7) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      int t = 4 * s + fq;
-      t = t < 27 ? t : 26;
-      toff[s] = goff(t);
-    }
-  } else {
-    toff[0] = goff(kC1F2[RO][fq]);
-    toff[1] = goff(kC1F2[RO][4 + fq]);
-    toff[2] = goff(kC1D2[RO][fq]);
-    toff[3 % KS] = goff(kC1W[fq]);
-    gh = goff(kC1H2[RO][fq]);
-    gx1 = goff(kC1X1[fq]);
-    gx2 = goff(kC1X2[fq]);
-    xsrc2 = fq == 2;
-    xsel1 = fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0100u : 0x05040100u;
-    xsel2 = fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0c0cu : 0x05040100u;
-  }
+  toff[0] = goff(kC1F[fq]);
+  toff[1] = goff(kC1F[4 + fq]);
+  toff[2] = goff(kC1D[fq]);
+  toff[3] = goff(kC1W[fq]);
+  const int gh = goff(kC1H[fq]);
+  const int gx1 = goff(kC1X1[fq]);
+  const int gx2 = goff(kC1X2[fq]);
+  const bool xsrc2 = fq == 2;
+  const uint32_t xsel1 = fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0100u : 0x05040100u;
+  const uint32_t xsel2 = fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0c0cu : 0x05040100u;
   const int colbase0 = (15 * (2 * op) + fr) * 8, colbase1 = colbase0 + 15 * 8;
   const int wloc = fr / 3, dw = fr - 3 * wloc;
   C1_STORE(0)
@@ -570,7 +506,9 @@ __global__ __launch_bounds__(256, OCC) void k_conv1_fwd_pool_pipe(const uint8_t*
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) best[i][j][r] = -INFINITY;
-#pragma unroll DDU
+    // the three dd rows unrolled: each row's pooling epilogue overlaps the next row's MFMAs and the body needs 208
+    // instead of 248 VGPRs (4.30 -> 4.17 ms per 64-client step, profiles/r3_ab_conv1_fwd_ddu.txt)
+#pragma unroll 3
     for (int dd = 0; dd < 3; ++dd) {
       // 3 KS k-steps (3 dh rows x KS); the B fragments are read PF steps ahead of their MFMAs (a ring of PF + 1
       // register pairs), so an LDS read's latency is covered by PF steps of matrix work, not one
@@ -579,8 +517,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv1_fwd_pool_pipe(const uint8_t*
 #pragma unroll
       for (int p = 0; p < PF; ++p) {
         const int ro = ((dd * 5 + p / KS) * HX) * 8;
-        rb0[p] = c1_bfrag<KS>(hb + colbase0, p % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
-        rb1[p] = c1_bfrag<KS>(hb + colbase1, p % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
+        rb0[p] = c1_bfrag(hb + colbase0, p % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
+        rb1[p] = c1_bfrag(hb + colbase1, p % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
       }
       f32x4 acc[2][2];
 #pragma unroll
@@ -594,8 +532,8 @@ __global__ __launch_bounds__(256, OCC) void k_conv1_fwd_pool_pipe(const uint8_t*
         }
         if (q + PF < NQ) {
           const int qn = q + PF, ro = ((dd * 5 + qn / KS) * HX) * 8;
-          rb0[qn % (PF + 1)] = c1_bfrag<KS>(hb + colbase0, qn % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
-          rb1[qn % (PF + 1)] = c1_bfrag<KS>(hb + colbase1, qn % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
+          rb0[qn % (PF + 1)] = c1_bfrag(hb + colbase0, qn % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
+          rb1[qn % (PF + 1)] = c1_bfrag(hb + colbase1, qn % KS, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
         }
         const f16x8 fb0 = rb0[q % (PF + 1)], fb1 = rb1[q % (PF + 1)];
 #pragma unroll
@@ -603,7 +541,7 @@ __global__ __launch_bounds__(256, OCC) void k_conv1_fwd_pool_pipe(const uint8_t*
           acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[i][s], fb0, acc[i][0], 0, 0, 0);
           acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[i][s], fb1, acc[i][1], 0, 0, 0);
         }
-        if (PF > 1) asm volatile("" ::: "memory");  // keep step q+PF's LDS reads in step q (no re-hoisting)
+        asm volatile("" ::: "memory");  // keep step q+PF's LDS reads in step q (no re-hoisting)
         if (s != KS - 1) continue;
         const uint32_t tag = (uint32_t)(dd * 9 + dh * 3 + dw);
 #pragma unroll
@@ -682,13 +620,13 @@ __device__ __forceinline__ void pool3_dpp4(const float (&b)[4], float (&m)[4]) {
 // (v_perm / v_cndmask / v_mov of k-steps 2-3).  The A operand (64 x 128 f16) stays in 64 VGPRs.  Halo loads are
 // unconditional (columns >= 61 clamp to 60: they only feed conv columns >= 59, which no pooled cell reads) with a
 // scalar row base and a per-thread 32-bit offset; the max-pool starts from the first candidate pair instead of -inf.
-template <int PF, int RO>
 __global__ __launch_bounds__(256, 2) void k_conv1_fwd_w64(const uint8_t* __restrict__ x8, const int* __restrict__ idx,
                                                           const uint16_t* __restrict__ w8,
                                                           const float* __restrict__ scale,
                                                           const float* __restrict__ shift, int B,
                                                           uint16_t* __restrict__ out, uint8_t* __restrict__ amax,
                                                           int nq) {
+  constexpr int PF = 2;                          // B-fragment prefetch distance in k-steps
   constexpr int HX = 64, KS = 4, KW = KS * 32;
   constexpr int HALO = 5 * 5 * HX * 8;           // f16 elements per buffer
   constexpr int NV = 5 * 5 * HX;                 // 1600 halo voxels
@@ -755,47 +693,22 @@ __global__ __launch_bounds__(256, 2) void k_conv1_fwd_w64(const uint8_t* __restr
     for (int r = 0; r < 4; ++r) asm volatile("" : "+v"(cinit[i][r]));
   }
   auto goff = [](int t) { return (((t / 9) * 5 + (t / 3) % 3) * HX + (t % 3)) * 8; };
-  constexpr int R1 = RO ? 1 : 0;
   int toff[KS];
-  toff[0] = goff(kC1F2[R1][fq]);
-  toff[1] = goff(kC1F2[R1][4 + fq]);
-  toff[2] = goff(kC1D2[R1][fq]);
+  toff[0] = goff(kC1F[fq]);
+  toff[1] = goff(kC1F[4 + fq]);
+  toff[2] = goff(kC1D[fq]);
   toff[3] = goff(kC1W[fq]);
-  const int gh = goff(kC1H2[R1][fq]);
-  // RO = 2: the empty X1 quarter (fq 3) reads the DHW group of its jw-paired quarter (zero weights)
-  const int gx1 = RO == 2 ? goff(kC1X1b[fq < 3 ? fq : 2]) : goff(kC1X1[fq]);
-  const int gx2 = RO == 2 ? goff(kC1X2b[fq]) : goff(kC1X2[fq]);
+  const int gh = goff(kC1H[fq]);
+  const int gx1 = goff(kC1X1[fq]);
+  const int gx2 = goff(kC1X2[fq]);
   const bool xsrc2 = fq == 2;
   const uint32_t xsel1 = fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0100u : 0x05040100u;
-  const uint32_t xsel2 = RO == 2 ? (fq < 2 ? 0x03020100u : 0x05040100u)
-                                 : fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0c0cu : 0x05040100u;
+  const uint32_t xsel2 = fq == 0 ? 0x03020100u : fq == 3 ? 0x0c0c0c0cu : 0x05040100u;
   // k-step 3's two 2-phase groups: the second dword of each is picked by address (dword 2 for the HW groups of
   // fq = 2, dword 1 otherwise) instead of a v_cndmask after a 16-B read
   const int gx1s = gx1 + (xsrc2 ? 4 : 2), gx2s = gx2 + (xsrc2 ? 4 : 2);
-  // a whole 16-B read whose value is only partly used: the opaque asm keeps all four dwords live, so the load is
-  // not narrowed back to a conflicting ds_read_b64 / ds_read2_b32
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  auto rd128 = [](const uint16_t* p) -> uint4 {
-    u32x4 v = *reinterpret_cast<const u32x4*>(p);
-    asm("" : "+v"(v));
-    return make_uint4(v[0], v[1], v[2], v[3]);
-  };
   auto bfrag = [&](const uint16_t* hb, int s, int ro) -> f16x8 {
-    if (RO == 2) {
-      if (s < 2) return *reinterpret_cast<const f16x8*>(&hb[ro + toff[s]]);
-      if (s == 2) {
-        const uint4 d = rd128(&hb[ro + toff[2]]), h = rd128(&hb[ro + gh]);
-        return __builtin_bit_cast(f16x8, make_uint4(d.x, d.y, h.x, h.z));  // D: phases 0-3, H: phases 0,1,4,5
-      }
-      const uint4 w = rd128(&hb[ro + toff[3]]), a = rd128(&hb[ro + gx1]), b = rd128(&hb[ro + gx2]);
-      uint4 v;
-      v.x = __builtin_amdgcn_perm(w.y, w.x, 0x05040100u);  // W: phases 0, 2
-      v.y = __builtin_amdgcn_perm(w.w, w.z, 0x05040100u);  // W: phases 4, 6
-      v.z = __builtin_amdgcn_perm(a.y, a.x, 0x05040100u);  // X1: phases 0, 2
-      v.w = __builtin_amdgcn_perm(b.z, b.x, xsel2);        // X2: phases 0, 1 (DH) or 0, 4 (HW)
-      return __builtin_bit_cast(f16x8, v);
-    }
-    if (s < 3) return c1_bfrag<KS>(hb, s, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
+    if (s < 3) return c1_bfrag(hb, s, ro, toff, gh, gx1, gx2, xsrc2, xsel1, xsel2);
     const uint4 w = *reinterpret_cast<const uint4*>(&hb[ro + toff[3]]);
     const uint32_t a0 = *reinterpret_cast<const uint32_t*>(&hb[ro + gx1]);
     const uint32_t a1 = *reinterpret_cast<const uint32_t*>(&hb[ro + gx1s]);
@@ -838,7 +751,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1_fwd_w64(const uint8_t* __restr
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[i][s], fb, s == 0 ? cinit[i] : acc[i], 0, 0, 0);
-        if (PF > 1) asm volatile("" ::: "memory");
+        asm volatile("" ::: "memory");
         if (s != KS - 1) continue;
         // the 9 (dd, dh) candidates of a lane fold into the running max with 4 v_max3: k = 0, 1 wait, k = 2 starts
         // the max, then every even k folds itself and the odd one before it
@@ -891,80 +804,25 @@ __global__ __launch_bounds__(256, 2) void k_conv1_fwd_w64(const uint8_t* __restr
   }
 }
 
-// forward variant: NIDT_C1_FWD=1 (default) the wave-tile kernel (k_conv1_fwd_w64: 4.20 -> 3.33 ms per 64-client
-// step, 0.59 -> 0.47 ms at 8 clients, profiles/r5_c1fwd_w64.txt), 0 the channel-split pipe kernel;
-// conv1_fwd_mode(m) overrides it at run time (tests: m = 0 / 1, -1 back to the environment / default)
+// forward kernel (test hook): 1 = the wave-tile kernel (k_conv1_fwd_w64: 4.20 -> 3.33 ms per 64-client step, 0.59 ->
+// 0.47 ms at 8 clients, profiles/r5_c1fwd_w64.txt), 0 = the channel-split pipe kernel (the tests' reference); -1 =
+// the default, 1
 static int g_c1fwd_mode = -1;
 void conv1_fwd_mode(int mode) { g_c1fwd_mode = mode; }
-int conv1_fwd_variant() {
-  static const int v = env_int("NIDT_C1_FWD", 1);
-  return g_c1fwd_mode >= 0 ? g_c1fwd_mode : v;
-}
 
 void conv1_fwd_pool(uintptr_t x8, uintptr_t idx, uintptr_t w8, uintptr_t scale, uintptr_t shift, int NB, int B,
                     uintptr_t out, uintptr_t amax, uintptr_t stream) {
   NIDT_REQUIRE(NB % B == 0, "conv1_fwd_pool: NB % B");
-  if (conv1_fwd_variant() == 1 && conv1_kslots() == 128) {
-    static const int nq1 = std::max(1, std::min(kPH, env_int("NIDT_C1_NQ", 1)));
-    // B-fragment prefetch distance of the RO = 2 kernel in k-steps (NIDT_C1_WPF, A/B), default 4 (3.28 ms per
-    // 64-client step vs 3.35 at 2; the RO = 0 kernel, 45.7 % bank conflicts, also 3.28: profiles/r6_conv1_b128.txt)
-    static const int wpf = env_int("NIDT_C1_WPF", 4);
-    if (conv1_tapord() == 2 && wpf == 3)
-      hipLaunchKernelGGL((k_conv1_fwd_w64<3, 2>), dim3(kPD * NB * nq1), dim3(256), 0, as_stream(stream),
-                         ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                         ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq1);
-    else if (conv1_tapord() == 2 && wpf == 4)
-      hipLaunchKernelGGL((k_conv1_fwd_w64<4, 2>), dim3(kPD * NB * nq1), dim3(256), 0, as_stream(stream),
-                         ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                         ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq1);
-    else if (conv1_tapord() == 2)
-      hipLaunchKernelGGL((k_conv1_fwd_w64<2, 2>), dim3(kPD * NB * nq1), dim3(256), 0, as_stream(stream),
-                         ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                         ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq1);
-    else if (conv1_tapord() == 1)
-      hipLaunchKernelGGL((k_conv1_fwd_w64<2, 1>), dim3(kPD * NB * nq1), dim3(256), 0, as_stream(stream),
-                         ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                         ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq1);
-    else
-      hipLaunchKernelGGL((k_conv1_fwd_w64<2, 0>), dim3(kPD * NB * nq1), dim3(256), 0, as_stream(stream),
-                         ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                         ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq1);
-    NIDT_CHECK(hipGetLastError());
-    return;
-  }
-  // B-fragment prefetch distance (k-steps); NIDT_C1_PF=1/2/3 selects it (A/B), default 2
-  static const int pf = env_int("NIDT_C1_PF", 2);
-  static const int occ = env_int("NIDT_C1_OCC", 2);
-  // pooled-row split per slab: NIDT_C1_NQ (A/B), default 1
-  static const int nq_env = std::max(1, std::min(kPH, env_int("NIDT_C1_NQ", 1)));
-  const int nq = nq_env;
-#define NIDT_C1(PF, KSS)                                                                                       \
-  if (occ == 3 && (PF) == 2 && (KSS) == 4)                                                                     \
-    hipLaunchKernelGGL((k_conv1_fwd_pool_pipe<2, 4, 3>), dim3(kPD * NB * nq), dim3(256), 0, as_stream(stream),     \
-                       ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale), \
-                       ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq);                      \
-  else                                                                                                         \
-  hipLaunchKernelGGL((k_conv1_fwd_pool_pipe<PF, KSS>), dim3(kPD * NB * nq), dim3(256), 0, as_stream(stream),      \
-                     ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),  \
-                     ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq)
-  // the three dd rows of the 3^3 window unrolled: each row's pooling epilogue overlaps the next row's MFMAs and the
-  // body needs 208 instead of 248 VGPRs (4.30 -> 4.17 ms per 64-client step, profiles/r3_ab_conv1_fwd_ddu.txt);
-  // NIDT_C1_DDU=1 keeps the rolled loop (A/B)
-  static const int ddu = env_int("NIDT_C1_DDU", 3);
-  if (conv1_kslots() == 128 && ddu == 3 && pf == 2 && occ != 3 && conv1_tapord() == 0) {
-    hipLaunchKernelGGL((k_conv1_fwd_pool_pipe<2, 4, 2, 3, 0>), dim3(kPD * NB * nq), dim3(256), 0, as_stream(stream),
+  const int mode = g_c1fwd_mode >= 0 ? g_c1fwd_mode : 1;
+  NIDT_REQUIRE(mode == 0 || mode == 1, "conv1_fwd_pool: mode must be 0 (pipe), 1 (wave tile) or -1 (default)");
+  if (mode == 1)
+    hipLaunchKernelGGL(k_conv1_fwd_w64, dim3(kPD * NB), dim3(256), 0, as_stream(stream),
                        ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                       ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq);
-  } else if (conv1_kslots() == 128 && ddu == 3 && pf == 2 && occ != 3) {
-    hipLaunchKernelGGL((k_conv1_fwd_pool_pipe<2, 4, 2, 3>), dim3(kPD * NB * nq), dim3(256), 0, as_stream(stream),
+                       ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), 1);
+  else
+    hipLaunchKernelGGL(k_conv1_fwd_pool_pipe, dim3(kPD * NB), dim3(256), 0, as_stream(stream),
                        ptr<const uint8_t>(x8), ptr<const int>(idx), ptr<const uint16_t>(w8), ptr<const float>(scale),
-                       ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), nq);
-  } else if (conv1_kslots() == 128) {
-    if (pf == 1) NIDT_C1(1, 4); else if (pf == 3) NIDT_C1(3, 4); else NIDT_C1(2, 4);
-  } else {
-    if (pf == 1) NIDT_C1(1, 7); else if (pf == 3) NIDT_C1(3, 7); else NIDT_C1(2, 7);
-  }
-#undef NIDT_C1
+                       ptr<const float>(shift), B, ptr<uint16_t>(out), ptr<uint8_t>(amax), 1);
   NIDT_CHECK(hipGetLastError());
 }
 
@@ -1090,10 +948,6 @@ template <> struct WgSet<1> { static constexpr int n = 4; __device__ static cons
 template <> struct WgSet<2> { static constexpr int n = 8; __device__ static constexpr int t(int i) { return kWgSet2[i]; } };
 template <> struct WgSet<3> { static constexpr int n = 11; __device__ static constexpr int t(int i) { return kWgSet3[i]; } };
 
-__host__ __device__ constexpr int tp_count(int t) {
-  return (t / 9 < 2 ? 2 : 1) * ((t / 3) % 3 < 2 ? 2 : 1) * (t % 3 < 2 ? 2 : 1);
-}
-
 // byte b of w as fp32: one v_cvt_f32_ubyteN.  Written out because the compiler merges the two dwords of a
 // ds_read_b64 into one 64-bit value for some tap sets and then converts (w64 >> 8n) & 0xff through the u64->f32
 // sequence (lshl_b64, min, or, cvt_f32_u32, ldexp: ~5 VALU per byte, ~20 extra per cell on waves 1-2, which
@@ -1154,7 +1008,7 @@ __device__ __forceinline__ void conv1_wg_fma(float dz, const uint2 (&u)[SET::n],
   if (slot & 1) S2[slot >> 1].x = fmaf(dz, pend, S2[slot >> 1].x);
 }
 
-template <int W, int UNR>
+template <int W>
 __device__ __forceinline__ void conv1_wg_wave(const uint8_t* __restrict__ xs, const uint16_t* __restrict__ dp,
                                               const uint16_t* __restrict__ pout, const uint8_t* __restrict__ amax,
                                               float* __restrict__ part, uint2* halo, uint32_t* meta, int n, int pd,
@@ -1189,21 +1043,7 @@ __device__ __forceinline__ void conv1_wg_wave(const uint8_t* __restrict__ xs, co
       meta[e] = dzb | ((uint32_t)off << 16);
     }
     __syncthreads();
-    // UNR cells per iteration: every cell's metadata and halo reads are issued before any of their FMAs, so the
-    // LDS latency of cell it+1 hides behind cell it's arithmetic inside one wave
-    int it = 0;
-    for (; it + UNR <= ncell; it += UNR) {
-      float dz[UNR];
-      uint2 u[UNR][SET::n];
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) conv1_wg_load<SET>(meta, halo, it + q, c, dz[q], u[q]);
-#pragma unroll
-      for (int q = 0; q < UNR; ++q) {
-        if (W == 0) Dsum += dz[q];
-        conv1_wg_fma<SET>(dz[q], u[q], S2);
-      }
-    }
-    for (; it < ncell; ++it) {
+    for (int it = 0; it < ncell; ++it) {
       float dz;
       uint2 u[SET::n];
       conv1_wg_load<SET>(meta, halo, it, c, dz, u);
@@ -1229,7 +1069,6 @@ __device__ __forceinline__ void conv1_wg_wave(const uint8_t* __restrict__ xs, co
 
 // grid = NB * 19 * nq: block (n, pd, q) walks pooled rows [q * rq, (q + 1) * rq) of its slab (nq = 2 when one
 // slab per (sample, pd) would give the chip fewer than ~4 blocks per CU: few clients per GPU)
-template <int UNR>
 __global__ __launch_bounds__(256) void k_conv1_wgrad_split(const uint8_t* __restrict__ x8, const int* __restrict__ idx,
                                                            const uint16_t* __restrict__ dp,
                                                            const uint16_t* __restrict__ pout,
@@ -1245,510 +1084,22 @@ __global__ __launch_bounds__(256) void k_conv1_wgrad_split(const uint8_t* __rest
   const int tid = threadIdx.x, c = tid & 63, wid = tid >> 6;
   const uint8_t* xs = x8 + (int64_t)idx[n] * kPZ * kPY * kPX * 8;
   switch (wid) {
-    case 0: conv1_wg_wave<0, UNR>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-    case 1: conv1_wg_wave<1, UNR>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-    case 2: conv1_wg_wave<2, UNR>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-    default: conv1_wg_wave<3, UNR>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
+    case 0: conv1_wg_wave<0>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
+    case 1: conv1_wg_wave<1>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
+    case 2: conv1_wg_wave<2>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
+    default: conv1_wg_wave<3>(xs, dp, pout, amax, part, halo, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
   }
 }
 
-// k_conv1_wgrad_dot — the same sparse wgrad with CELL-PAIRED bf16 dot products: uint8 inputs are exact in bf16, so
-// the halo is staged once per stage as bf16 (two planes of 4 phases, each an 8-B voxel read with the padded strides
-// above: the 27 argmax offsets stay on 27 distinct bank pairs), and each lane takes two cells at a time:
-// v_perm_b32 interleaves the two cells' values of a tap into one bf16 pair and v_dot2c_f32_bf16 adds both products
-// to the tap's fp32 accumulator — 1 VALU per MAC (one perm + one dot2 per two MACs) instead of 1.5
-// (v_cvt_f32_ubyte per value + half a v_pk_fma_f32).  The dz pair (bf16, as stored) is one perm per cell pair.
-__device__ __forceinline__ uint32_t bf2_pack(float lo, float hi) {  // exact for integers < 257
+// exact bf16 pair of two integers < 257 held as fp32
+__device__ __forceinline__ uint32_t bf2_pack(float lo, float hi) {
   return __builtin_amdgcn_perm(__float_as_uint(hi), __float_as_uint(lo), 0x07060302u);
 }
-typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float dot2bf(uint32_t a, uint32_t b, float c) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2v, a), __builtin_bit_cast(bf16x2v, b), c, false);
-}
 
-// the 8-B halo reads of one cell for a wave's tap set: phases 0-3 (hlo) of every group that has a live tap there,
-// then phases 4-7 (hhi)
-template <class SET>
-__device__ constexpr int wd_nreads() {
-  int n = 0;
-  for (int h = 0; h < 2; ++h)
-    for (int i = 0; i < SET::n; ++i) {
-      bool need = false;
-      for (int r = 0; r < 4; ++r) need = need || tp_valid(SET::t(i), 4 * h + r);
-      n += need ? 1 : 0;
-    }
-  return n;
-}
-
-// volatile 8-B reads: one ds_read_b64 each (2 LDS cycles, 64-bank rule), issued in this order.  Plain loads of
-// neighbouring voxels get merged into ds_read2_b64 (8 cycles for the same 16 B, 32-bank rule: the padded strides
-// no longer separate the argmax offsets) or split into ds_read2_b32.
+// volatile 8-B LDS read: one ds_read_b64, issued in program order (never merged into ds_read2_b64 or split into
+// ds_read2_b32: see conv1_wg_load)
 typedef const volatile __attribute__((address_space(3))) uint64_t lds_u64;
-template <class SET, int NR>
-__device__ __forceinline__ void conv1_wd_load(const uint2* hlo, const uint2* hhi, uint32_t m, uint64_t (&v)[NR]) {
-  int k = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < SET::n; ++i) {
-      const int t = SET::t(i);
-      bool need = false;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) need = need || tp_valid(t, 4 * h + r);
-      if (!need) continue;
-      const int off = (t / 9) * kWgZS + ((t / 3) % 3) * kWgRS + t % 3;
-      v[k++] = ((lds_u64*)((h ? hhi : hlo) + (m >> 16)))[off];
-    }
-}
-
-template <class SET, int NR>
-__device__ __forceinline__ void conv1_wd_fma(uint32_t dzp, const uint64_t (&a)[NR], const uint64_t (&b)[NR], float* S) {
-  int k = 0, slot = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < SET::n; ++i) {
-      const int t = SET::t(i);
-      bool need = false;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) need = need || tp_valid(t, 4 * h + r);
-      if (!need) continue;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const uint32_t aj = (uint32_t)(a[k] >> (32 * j)), bj = (uint32_t)(b[k] >> (32 * j));
-        if (tp_valid(t, 4 * h + 2 * j)) {
-          S[slot] = dot2bf(dzp, __builtin_amdgcn_perm(bj, aj, 0x05040100u), S[slot]);
-          ++slot;
-        }
-        if (tp_valid(t, 4 * h + 2 * j + 1)) {
-          S[slot] = dot2bf(dzp, __builtin_amdgcn_perm(bj, aj, 0x07060302u), S[slot]);
-          ++slot;
-        }
-      }
-      ++k;
-    }
-}
-
-// slot order of the accumulators: phases 0-3 of every group of the set, then phases 4-7 (conv1_wd_half order)
-template <class SET>
-__device__ __forceinline__ void conv1_wd_store(const float* S, float* op) {
-  int slot = 0;
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < SET::n; ++i) {
-      const int t = SET::t(i);
-      bool need = false;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) need = need || tp_valid(t, 4 * h + r);
-      if (!need) continue;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (tp_valid(t, 4 * h + r)) op[tp_to_k(t, 4 * h + r)] = S[slot++];
-    }
-}
-
-template <int W>
-__device__ __forceinline__ void conv1_wd_wave(const uint8_t* __restrict__ xs, const uint16_t* __restrict__ dp,
-                                              const uint16_t* __restrict__ pout, const uint8_t* __restrict__ amax,
-                                              float* __restrict__ part, uint2* hlo, uint2* hhi, uint32_t* meta, int n,
-                                              int pd, int tid, int c, int ph_begin, int ph_end, int slab) {
-  using SET = WgSet<W>;
-  constexpr int NS = 32;
-  float S[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) S[k] = 0.f;
-  float Dsum = 0.f;
-  const int64_t rowbase = ((int64_t)n * kPD + pd) * kPH;
-  // the next stage's global reads (halo voxels, pooled value / gradient / argmax per (cell, channel)) are issued into
-  // registers before this stage's dot products and written to LDS after them: with 54 KB of LDS per block only 2
-  // blocks share a CU, too few to cover the staging latency by switching blocks
-  constexpr int kHV = (5 * kWgHY * 64 + 255) / 256, kMV = (kWgMeta + 255) / 256;
-  uint2 hv[kHV];
-  uint16_t pvr[kMV], gvr[kMV];
-  uint8_t avr[kMV];
-  auto prefetch = [&](int ph0) {
-    const int nph = min(kWgRows, ph_end - ph0), ny = 3 * nph + 2, ncell = nph * kPW;
-    const int64_t obase = ((rowbase + ph0) * kPW) * kC1;
-#pragma unroll
-    for (int k = 0; k < kHV; ++k) {
-      const int e = tid + 256 * k;
-      const int xh = e & 63, r = e >> 6, yh = r % ny, zh = r / ny;
-      hv[k] = make_uint2(0, 0);
-      if (e < 5 * ny * 64 && xh < kPX)
-        hv[k] = *reinterpret_cast<const uint2*>(xs + (((int64_t)(3 * pd + zh) * kPY + 3 * ph0 + yh) * kPX + xh) * 8);
-    }
-#pragma unroll
-    for (int k = 0; k < kMV; ++k) {
-      const int e = tid + 256 * k;
-      if (e < ncell * kC1) {
-        pvr[k] = pout[obase + e];
-        gvr[k] = dp[obase + e];
-        avr[k] = amax[obase + e];
-      }
-    }
-  };
-  auto commit = [&](int ph0) {
-    const int nph = min(kWgRows, ph_end - ph0), ny = 3 * nph + 2, ncell = nph * kPW;
-#pragma unroll
-    for (int k = 0; k < kHV; ++k) {
-      const int e = tid + 256 * k;
-      if (e < 5 * ny * 64) {
-        const int xh = e & 63, r = e >> 6, yh = r % ny, zh = r / ny;
-        const int hi = zh * kWgZS + yh * kWgRS + xh;
-        const uint2 v = hv[k];
-        hlo[hi] = make_uint2(bf2_pack(u8f(v.x, 0), u8f(v.x, 1)), bf2_pack(u8f(v.x, 2), u8f(v.x, 3)));
-        hhi[hi] = make_uint2(bf2_pack(u8f(v.y, 0), u8f(v.y, 1)), bf2_pack(u8f(v.y, 2), u8f(v.y, 3)));
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < kMV; ++k) {
-      const int e = tid + 256 * k;
-      if (e < ncell * kC1) {
-        const int cell = e >> 6, a = avr[k];
-        const int phl = cell / kPW, pw = cell - phl * kPW;
-        const int off = (a / 9) * kWgZS + (3 * phl + (a / 3) % 3) * kWgRS + 3 * pw + a % 3;
-        const uint32_t dzb = bf16_to_f32(pvr[k]) > 0.f ? (uint32_t)gvr[k] : 0u;
-        meta[e] = dzb | ((uint32_t)off << 16);
-      }
-    }
-  };
-  prefetch(ph_begin);
-  for (int ph0 = ph_begin; ph0 < ph_end; ph0 += kWgRows) {
-    const int nph = min(kWgRows, ph_end - ph0);
-    const int ncell = nph * kPW;
-    __syncthreads();  // previous stage's reads done
-    commit(ph0);
-    __syncthreads();
-    if (ph0 + kWgRows < ph_end) prefetch(ph0 + kWgRows);
-    // two cells per step; the next pair's halo reads are issued before this pair's dot products (registers X/Y
-    // alternate, so no copies)
-    constexpr int NR = wd_nreads<SET>();
-    auto pair_meta = [&](int it, uint32_t& m0, uint32_t& m1) {
-      m0 = meta[it * kC1 + c];
-      m1 = it + 1 < ncell ? meta[(it + 1) * kC1 + c] : (m0 & 0xffff0000u);  // odd tail: dz = 0
-    };
-    auto pair_fma = [&](uint32_t m0, uint32_t m1, const uint64_t (&a)[NR], const uint64_t (&b)[NR]) {
-      if (W == 0) Dsum += bf16_to_f32((uint16_t)(m0 & 0xffffu)) + bf16_to_f32((uint16_t)(m1 & 0xffffu));
-      conv1_wd_fma<SET, NR>(__builtin_amdgcn_perm(m1, m0, 0x05040100u), a, b, S);  // dz pair (dz0, dz1)
-    };
-    uint64_t xa[NR], xb[NR], ya[NR], yb[NR];
-    uint32_t xm0, xm1, ym0, ym1;
-    pair_meta(0, xm0, xm1);
-    conv1_wd_load<SET, NR>(hlo, hhi, xm0, xa);
-    conv1_wd_load<SET, NR>(hlo, hhi, xm1, xb);
-    for (int it = 0; it < ncell; it += 4) {
-      const bool more1 = it + 2 < ncell, more2 = it + 4 < ncell;
-      if (more1) {
-        pair_meta(it + 2, ym0, ym1);
-        conv1_wd_load<SET, NR>(hlo, hhi, ym0, ya);
-        conv1_wd_load<SET, NR>(hlo, hhi, ym1, yb);
-      }
-      pair_fma(xm0, xm1, xa, xb);
-      if (!more1) break;
-      if (more2) {
-        pair_meta(it + 4, xm0, xm1);
-        conv1_wd_load<SET, NR>(hlo, hhi, xm0, xa);
-        conv1_wd_load<SET, NR>(hlo, hhi, xm1, xb);
-      }
-      pair_fma(ym0, ym1, ya, yb);
-    }
-  }
-  float* op = part + ((int64_t)slab * kC1 + c) * 126;
-  conv1_wd_store<SET>(S, op);
-  if (W == 0) op[125] = Dsum;
-}
-
-__global__ __launch_bounds__(256, 2) void k_conv1_wgrad_dot(const uint8_t* __restrict__ x8, const int* __restrict__ idx,
-                                                         const uint16_t* __restrict__ dp,
-                                                         const uint16_t* __restrict__ pout,
-                                                         const uint8_t* __restrict__ amax, float* __restrict__ part,
-                                                         int nq) {
-  __shared__ __attribute__((aligned(256))) uint2 hlo[kWgHalo];
-  __shared__ __attribute__((aligned(256))) uint2 hhi[kWgHalo];
-  __shared__ uint32_t meta[kWgMeta];
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int q = bid % nq, rest = bid / nq;
-  const int pd = rest % kPD, n = rest / kPD;
-  const int rq = ((kPH + nq - 1) / nq + kWgRows - 1) / kWgRows * kWgRows;
-  const int ph_begin = q * rq, ph_end = min(kPH, ph_begin + rq);
-  const int tid = threadIdx.x, c = tid & 63, wid = tid >> 6;
-  const uint8_t* xs = x8 + (int64_t)idx[n] * kPZ * kPY * kPX * 8;
-  switch (wid) {
-    case 0: conv1_wd_wave<0>(xs, dp, pout, amax, part, hlo, hhi, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-    case 1: conv1_wd_wave<1>(xs, dp, pout, amax, part, hlo, hhi, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-    case 2: conv1_wd_wave<2>(xs, dp, pout, amax, part, hlo, hhi, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-    default: conv1_wd_wave<3>(xs, dp, pout, amax, part, hlo, hhi, meta, n, pd, tid, c, ph_begin, ph_end, bid_slab(rest, q, nq)); break;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_conv1_wgrad_smf — the same S[c][k] / D[c] slabs on 2:4-sparse MATRIX cores (v_smfmac_f32_32x32x32_bf16).
-//
-// S[c][k] = sum_pos dY[c][pos] X[2 pos + k] over the conv-output positions of the pooled region, with dY = dz at each
-// (cell, channel)'s argmax voxel and 0 elsewhere — an implicit-GEMM weight gradient with M = 64 channels (2 tiles of
-// 32), N = 125 taps (4 tiles of 32, 3 dummy columns), K = the conv positions x of one conv row (57 live, 2 k-steps of
-// 32).  Along x a group of 4 consecutive positions touches at most 2 pooling cells (cells are 3 wide) and a cell has
-// exactly ONE argmax per channel, so each group of 4 K of a channel's dY row holds <= 2 non-zeros: dY is exactly 2:4
-// structured-sparse, and smfmac computes the dense-equivalent product at twice the dense MFMA rate (the 32x32x32
-// smfmac issues at the cycles of the dense 32x32x16: profiles/r4_smfmac_probe.txt).  This replaces the per-(cell,
-// channel) gather on the VALU (k_conv1_wgrad_split: 0 MFMA, ~35 TF/s).
-//
-// Operand layouts (gfx950, measured with tools/probes/smfmac_probe.hip): B lane (n = l % 32, q = l / 32) holds the 16
-// consecutive K = 16 q .. 16 q + 15 of column n; A lane (m = l % 32, p = l / 32) holds 8 compressed values, element j
-// covering the 4-group at K = 16 (j >> 2) + 8 p + 4 ((j >> 1) & 1), its position in that group in bits 2j..2j+1 of
-// the index VGPR (abid 0).  With K = x, tap k = (kd, kh, kw)'s B fragment is 16 consecutive x of the input's phase
-// plane r(k) shifted by jw = kw >> 1.  Misaligned ds_read_b128 are exact on gfx950 but ~11x slower (probe), so the
-// stage holds three shifted copies J = jw of the bf16 phase planes (J = 2 only for rw = 0: 20 planes), laid out by
-// tools/probes/c1wg_layout_gen.py so that no ds_read_b128 lane group has two taps on one bank.
-//
-// A is built in registers: per stage each lane reads, for its 8 slots of each M-tile, the (dz, argmax) record of the
-// slot's cell from LDS and folds "argmax inside this 4-group" into a row key; per conv row a slot is dz if its key is
-// that row, else 0 (the position index word is row-independent).  Block = (sample, pd[, row range]), stage = pooled
-// row ph: wave w runs k-step w & 1 over 5 or 4 of the 9 conv rows (alternating per stage), 8 smfmac per row.  Slabs
-// are reduced across the 4 waves in a fixed order (deterministic), in the VALU kernel's part[slab][64][126] format.
-// Block = 8 waves, warp-specialised and double-buffered (one block per CU): waves 4-7 are producers — they issue the
-// global loads of stage s + 2, convert and store stage s + 1 (the 20 bf16 phase-plane copies and the record table)
-// into the other LDS buffer; waves 0-3 are consumers — each runs k-step w & 1 of stage s over 5 or 4 of its 9 conv
-// rows (8 smfmac per row, the next row's B fragments loaded under the current row's MFMAs).  One barrier per stage.
-constexpr int kSmBufBytes = (kC1sBElems * 2 + 15) / 16 * 16;        // one stage's B planes
-constexpr int kSmMetaBytes = kPW * kC1 * 4;                          // one stage's record table
-constexpr int kSmBytes = 2 * kSmBufBytes + 2 * kSmMetaBytes;
-static_assert(kSmBytes >= 4 * 32 * 128 * 4 + 4 * 64 * 4, "reduction scratch must fit in the stage buffers");
-static_assert(kSmBytes <= 160 * 1024, "LDS budget");
-
 typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-
-// producer side: one stage's global data held in registers between its load and its LDS store
-struct C1sStage {
-  uint2 vx[10];        // 10 polyphase voxels (x0 .. x0 + 9) of this thread's staged input row
-  uint32_t rpg[5];     // pooled value | dL/dpooled << 16 of this thread's 5 records
-  uint32_t ra[5];      // argmax of the records
-};
-
-__device__ __forceinline__ void c1s_load(C1sStage& st, const uint8_t* xs, const uint16_t* dp, const uint16_t* pout,
-                                         const uint8_t* amax, int64_t rowbase, int pd, int ph, int ptid) {
-  const int brow = ptid >> 3, bx0 = 8 * (ptid & 7);
-  const int bzi = brow / 5, byi = brow - 5 * (brow / 5);
-#pragma unroll
-  for (int v = 0; v < 10; ++v) {
-    const int x = bx0 + v;
-    st.vx[v] = make_uint2(0, 0);
-    if (ptid < 200 && x < kPX)
-      st.vx[v] = *reinterpret_cast<const uint2*>(xs + (((int64_t)(3 * pd + bzi) * kPY + 3 * ph + byi) * kPX + x) * 8);
-  }
-  const int rc = ptid & 63, rcg = ptid >> 6;
-  const int64_t obase = (rowbase + ph) * kPW * kC1;
-#pragma unroll
-  for (int u = 0; u < 5; ++u) {
-    const int pw = rcg + 4 * u;
-    st.rpg[u] = 0;
-    st.ra[u] = 0;
-    if (pw < kPW) {
-      st.rpg[u] = (uint32_t)pout[obase + pw * kC1 + rc] | ((uint32_t)dp[obase + pw * kC1 + rc] << 16);
-      st.ra[u] = amax[obase + pw * kC1 + rc];
-    }
-  }
-}
-
-__device__ __forceinline__ void c1s_store(const C1sStage& st, uint16_t* bsm, uint32_t* meta, int ptid, float& Dloc) {
-  if (ptid < 200) {
-    const int brow = ptid >> 3, bx0 = 8 * (ptid & 7);
-    const int bzi = brow / 5, byi = brow - 5 * (brow / 5);
-    const int roff = bzi * kC1sZS + byi * kC1sRS + bx0;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      float f[10];
-#pragma unroll
-      for (int v = 0; v < 10; ++v) f[v] = u8f(r < 4 ? st.vx[v].x : st.vx[v].y, r & 3);
-      const uint32_t e0 = bf2_pack(f[0], f[1]), e1 = bf2_pack(f[2], f[3]), e2 = bf2_pack(f[4], f[5]);
-      const uint32_t e3 = bf2_pack(f[6], f[7]), e4 = bf2_pack(f[8], f[9]);
-      *reinterpret_cast<uint4*>(&bsm[kC1sPlaneBase[kC1sPlaneOf[0][r]] + roff]) = make_uint4(e0, e1, e2, e3);
-      *reinterpret_cast<uint4*>(&bsm[kC1sPlaneBase[kC1sPlaneOf[1][r]] + roff]) =
-          make_uint4(bf2_pack(f[1], f[2]), bf2_pack(f[3], f[4]), bf2_pack(f[5], f[6]), bf2_pack(f[7], f[8]));
-      if ((r & 1) == 0)
-        *reinterpret_cast<uint4*>(&bsm[kC1sPlaneBase[kC1sPlaneOf[2][r]] + roff]) = make_uint4(e1, e2, e3, e4);
-    }
-  }
-  const int rc = ptid & 63, rcg = ptid >> 6;
-#pragma unroll
-  for (int u = 0; u < 5; ++u) {
-    const int pw = rcg + 4 * u;
-    const uint32_t dzb = bf16_to_f32((uint16_t)(st.rpg[u] & 0xffffu)) > 0.f ? (st.rpg[u] >> 16) : 0u;
-    Dloc += bf16_to_f32((uint16_t)dzb);
-    if (pw < kPW) {
-      const int a = st.ra[u];
-      const int ad = a / 9, ah = (a / 3) % 3, aw = a % 3;
-      meta[pw * kC1 + rc] = dzb | ((uint32_t)(3 * pw + aw) << 16) | ((uint32_t)(ad * 3 + ah) << 24);
-    }
-  }
-}
-
-__global__ __launch_bounds__(512, 1) void k_conv1_wgrad_smf(const uint8_t* __restrict__ x8, const int* __restrict__ idx,
-                                                           const uint16_t* __restrict__ dp,
-                                                           const uint16_t* __restrict__ pout,
-                                                           const uint8_t* __restrict__ amax, float* __restrict__ part,
-                                                           int nq) {
-  __shared__ __attribute__((aligned(16))) uint8_t smem[kSmBytes];
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int q = bid % nq, rest = bid / nq;
-  const int pd = rest % kPD, n = rest / kPD;
-  const int rq = ((kPH + nq - 1) / nq + kWgRows - 1) / kWgRows * kWgRows;
-  const int ph_begin = q * rq, ph_end = min(kPH, ph_begin + rq);
-  const int nst = ph_end - ph_begin;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const bool producer = wid >= 4;
-  const uint8_t* xs = x8 + (int64_t)idx[n] * kPZ * kPY * kPX * 8;
-  const int64_t rowbase = ((int64_t)n * kPD + pd) * kPH;
-  auto bbuf = [&](int s) { return reinterpret_cast<uint16_t*>(smem + (s & 1) * kSmBufBytes); };
-  auto mbuf = [&](int s) { return reinterpret_cast<uint32_t*>(smem + 2 * kSmBufBytes + (s & 1) * kSmMetaBytes); };
-
-  float Dloc = 0.f;
-  f32x16 acc[2][4];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int T = 0; T < 4; ++T)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[t][T][i] = 0.f;
-
-  if (producer) {  // ------------------------------------------------------------------------------ producers
-    const int ptid = tid - 256;
-    C1sStage cur, nxt;
-    c1s_load(cur, xs, dp, pout, amax, rowbase, pd, ph_begin, ptid);
-    if (nst > 1) c1s_load(nxt, xs, dp, pout, amax, rowbase, pd, ph_begin + 1, ptid);
-    c1s_store(cur, bbuf(0), mbuf(0), ptid, Dloc);
-    __syncthreads();                                  // stage 0 ready
-    for (int s = 0; s < nst; ++s) {
-      if (s + 1 < nst) {
-        cur = nxt;
-        if (s + 2 < nst) c1s_load(nxt, xs, dp, pout, amax, rowbase, pd, ph_begin + s + 2, ptid);
-        c1s_store(cur, bbuf(s + 1), mbuf(s + 1), ptid, Dloc);
-      }
-      __syncthreads();                                // stage s consumed, stage s + 1 ready
-    }
-  } else {  // ------------------------------------------------------------------------------------- consumers
-    const int ks = wid & 1;  // this wave's k-step (x 0-31 or 32-63)
-    int bbase[4];
-#pragma unroll
-    for (int T = 0; T < 4; ++T) {
-      int k = kC1sSlotTap[32 * T + (lane & 31)];
-      k = k >= 1000 ? k - 1000 : k;
-      const int kd = k / 25, kh = (k / 5) % 5, kw = k % 5;
-      const int r = ((kd & 1) << 2) | ((kh & 1) << 1) | (kw & 1);
-      bbase[T] = kC1sPlaneBase[kC1sPlaneOf[kw >> 1][r]] + (kd >> 1) * kC1sZS + (kh >> 1) * kC1sRS + 16 * (lane >> 5) +
-                 32 * ks;
-    }
-    // this lane's 4-groups g at x = xg (slot 0 = the group's first cell, slot 1 = the next one)
-    const int xg0 = 32 * ks + 8 * (lane >> 5);
-    __syncthreads();                                  // stage 0 ready
-    for (int s = 0; s < nst; ++s) {
-      const uint16_t* bsm = bbuf(s);
-      const uint32_t* meta = mbuf(s);
-      // per-stage A operands: per 4-group g the slots' dz values packed as one bf16 pair (W) and their conv rows as
-      // one-hot bits (low half slot 0, high half slot 1; none when the argmax falls outside the group); the index
-      // word holds each argmax's position in its group
-      uint32_t wv[2][4], oh[2][4], ix[2] = {0u, 0u};
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int xg = xg0 + 16 * (g >> 1) + 4 * (g & 1);
-        const int C0 = xg / 3;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          uint32_t w = 0, o = 0;
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int C = C0 + h;
-            const uint32_t mw = C < kPW ? meta[C * kC1 + 32 * t + (lane & 31)] : 0u;
-            const uint32_t d = ((mw >> 16) & 0xffu) - (uint32_t)xg;
-            const bool in = d <= 3u && C < kPW;
-            w |= (in ? (mw & 0xffffu) : 0u) << (16 * h);
-            o |= (in ? (1u << (mw >> 24)) : 0u) << (16 * h);
-            ix[t] |= (in ? d : 0u) << (2 * (2 * g + h));
-          }
-          wv[t][g] = w;
-          oh[t][g] = o;
-        }
-      }
-      const int half = (wid >> 1) ^ (s & 1);
-      const int rr0 = half ? 5 : 0, rr1 = half ? 9 : 5;
-      // B fragments of row rr: software-pipelined one row ahead
-      bf16x16 bv[4], bn[4];
-      auto loadB = [&](int rr, bf16x16 (&dst)[4]) {
-        const int roff = (rr / 3) * kC1sZS + (rr % 3) * kC1sRS;
-#pragma unroll
-        for (int T = 0; T < 4; ++T) {
-          const uint16_t* bp = &bsm[bbase[T] + roff];
-          const bf16x8 lo = *reinterpret_cast<const bf16x8*>(bp);
-          const bf16x8 hi = *reinterpret_cast<const bf16x8*>(bp + 8);
-          dst[T] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
-        }
-      };
-      loadB(rr0, bv);
-      for (int rr = rr0; rr < rr1; ++rr) {
-        if (rr + 1 < rr1) loadB(rr + 1, bn);
-        // A of row rr: shifting a one-hot pair left by 15 - rr puts bit rr of each half into that half's sign bit;
-        // a packed 16-bit arithmetic shift by 15 makes it a 0xffff / 0 mask per slot (3 VALU per 4-group)
-        bf16x8 av[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          uint32_t w[4];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const s16x2 sh = __builtin_bit_cast(s16x2, oh[t][g] << (15 - rr));
-            const s16x2 m = sh >> (s16x2){15, 15};
-            w[g] = wv[t][g] & __builtin_bit_cast(uint32_t, m);
-          }
-          av[t] = __builtin_bit_cast(bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
-        }
-#pragma unroll
-        for (int T = 0; T < 4; ++T) {
-          acc[0][T] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(av[0], bv[T], acc[0][T], (int)ix[0], 0, 0);
-          acc[1][T] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(av[1], bv[T], acc[1][T], (int)ix[1], 0, 0);
-        }
-#pragma unroll
-        for (int T = 0; T < 4; ++T) bv[T] = bn[T];
-      }
-      __syncthreads();                                // stage s consumed, stage s + 1 ready
-    }
-  }
-  // fixed-order reduction over the 4 consumer waves, one M-tile (32 channels) at a time, and D over the producers'
-  // 4 cell groups
-  float* red = reinterpret_cast<float*>(smem);           // [4 w][32 m][128 slot]
-  float* dred = red + 4 * 32 * 128;                      // [4 cg][64 c]
-  float* op = part + (int64_t)bid_slab(rest, q, nq) * kC1 * 126;
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    __syncthreads();
-    if (!producer) {
-#pragma unroll
-      for (int T = 0; T < 4; ++T)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int m = 8 * (i >> 2) + 4 * (lane >> 5) + (i & 3);
-          red[(wid * 32 + m) * 128 + 32 * T + (lane & 31)] = acc[t][T][i];
-        }
-    } else if (t == 0) {
-      const int ptid = tid - 256;
-      dred[(ptid >> 6) * 64 + (ptid & 63)] = Dloc;
-    }
-    __syncthreads();
-    for (int e = tid; e < 32 * 126; e += 512) {
-      const int m = e / 126, k = e - 126 * (e / 126);
-      float v;
-      if (k < 125) {
-        const int sl = kC1sTapSlot[k];
-        v = red[(0 * 32 + m) * 128 + sl] + red[(1 * 32 + m) * 128 + sl];
-        v += red[(2 * 32 + m) * 128 + sl] + red[(3 * 32 + m) * 128 + sl];
-      } else {
-        const int c = 32 * t + m;
-        v = dred[0 * 64 + c] + dred[1 * 64 + c] + dred[2 * 64 + c] + dred[3 * 64 + c];
-      }
-      op[(32 * t + m) * 126 + k] = v;
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_conv1_wgrad_mx — the conv1 weight-gradient slabs on 2:4-sparse matrix cores with the argmax ROW in the sparsity
@@ -1757,13 +1108,17 @@ __global__ __launch_bounds__(512, 1) void k_conv1_wgrad_smf(const uint8_t* __res
 // K of S[c][k] = sum_pos dY[c][pos] X[2 pos + k] is ordered (dh, x, dd): a 4-group of K is the three conv positions
 // dd = 0, 1, 2 of one pooling-window column (dh, x) plus a pad slot.  A window column holds at most one argmax per
 // channel (a cell has one argmax, at (dd, dh, dw)), so every 4-group of a channel's dY row has <= 1 non-zero — legal
-// 2:4 — and its position in the group IS the argmax's dd.  Hence:
+// 2:4 — and its position in the group IS the argmax's dd.  The 32x32x32 smfmac issues at the cycles of the dense
+// 32x32x16 (profiles/r4_smfmac_probe.txt).  Operand layouts (gfx950, measured with tools/probes/smfmac_probe.hip): B
+// lane (n = l % 32, q = l / 32) holds the 16 consecutive K = 16 q .. 16 q + 15 of column n; A lane (m = l % 32, p =
+// l / 32) holds 8 compressed values, element j covering the 4-group at K = 16 (j >> 2) + 8 p + 4 ((j >> 1) & 1), its
+// position in that group in bits 2j..2j+1 of the index VGPR (abid 0).  Hence:
 //  * A (dY, 32 channels x 32 K per M-tile) is the same for the three dh of a pooled row: element 2i = dz of the
 //    cell covering the lane's x (dY = dz only where the argmax column is x: aw == x mod 3), element 2i + 1 = 0.  Only
 //    the 2-bit indices change with dh: dd where the argmax is in row dh, else 3 (the pad slot, whose B value is 0).
 //    The three index words come from ONE 32-bit OR per (channel, x) and stage — fields at bits 4i (dh 0), 16 + 4i
 //    (dh 1, read with abid 1) and 4i + 2 (dh 2: the dead element's field, read after a 2-bit shift) — instead of a
-//    per-row value mask (k_conv1_wgrad_smf: 23 VALU per smfmac);
+//    per-row value mask (23 VALU per smfmac);
 //  * B (input, 32 K x 32 taps per N-tile) comes from "dd-slot images": per jd = kd >> 1 an image of 4-slot groups
 //    [z' = 3 pd + jd + dd for dd = 0..2, 0] per (y', phase r, x'), so a tap's 16 K (4 groups at x' = x + jw) are 32
 //    contiguous bytes, 8-B aligned for every jw: no shifted copies, four ds_read_b64 per fragment, and all 125 taps
@@ -1864,7 +1219,6 @@ __device__ __forceinline__ MxStage mx_stage(int pd0, int S) {
   return MxStage{pd0 + sl, S - sl * kPH, (5 * sl) & 7};
 }
 
-template <int DBG>
 __global__ __launch_bounds__(512, 1) void k_conv1_wgrad_mx(const uint8_t* __restrict__ x8, const int* __restrict__ idx,
                                                           const uint16_t* __restrict__ dp,
                                                           const uint16_t* __restrict__ pout,
@@ -1981,7 +1335,7 @@ __global__ __launch_bounds__(512, 1) void k_conv1_wgrad_mx(const uint8_t* __rest
     Set sa, sb;
     auto load_stage = [&](Set& X, int S) {  // S clamped to a valid stage: the loads never sit under a branch
       S = min(S, nstage - 1);
-      const MxStage st = mx_stage(pd0, DBG ? 0 : S);  // DBG: diagnostic, every row re-reads stage 0 (L2 hits)
+      const MxStage st = mx_stage(pd0, S);
       if constexpr (META) {
 #pragma unroll
         for (int k = 0; k < NREC; ++k)
@@ -2134,8 +1488,8 @@ __global__ __launch_bounds__(512, 1) void k_conv1_wgrad_mx(const uint8_t* __rest
 // the grid still covers the chip ~4 times
 int conv1_wgrad_mx_npb(int NB) { return std::max(1, std::min(kPD, NB * kPD / (4 * 256))); }
 
-// conv1 weight-gradient kernel: 0 = VALU gather (k_conv1_wgrad_split), 1 = 2:4 smfmac (k_conv1_wgrad_smf),
-// 2 = 2:4 smfmac with the argmax row in the index (k_conv1_wgrad_mx); -1 = the environment default
+// conv1 weight-gradient kernel (test hook): 0 = VALU gather (k_conv1_wgrad_split, the tests' reference), 2 = 2:4 smfmac
+// with the argmax row in the index (k_conv1_wgrad_mx); -1 = the default, 2
 static int g_c1wg_mode = -1;
 void conv1_wgrad_mode(int mode) { g_c1wg_mode = mode; }
 
@@ -2147,44 +1501,21 @@ void conv1_wgrad(uintptr_t x8, uintptr_t idx, uintptr_t dp, uintptr_t pout, uint
                  int64_t goff_g, int64_t goff_b, float wscale, uintptr_t emean, uintptr_t stream) {
   hipStream_t s = as_stream(stream);
   const int nq = conv1_wgrad_nq(NB);
-  // NIDT_C1WG_UNROLL=2|4: unrolled cell loop (A/B: loads of the next cell overlap the current cell's FMAs)
-  static const int unr = env_int("NIDT_C1WG_UNROLL", 1);
-  // NIDT_C1WG_DOT=1: the cell-paired bf16 dot-product kernel (A/B record: 4.52 ms vs 3.98 ms for this one at
-  // 64 clients, profiles/r3_ab_conv1_wgrad_dot.txt — v_dot2c_f32_bf16 does not issue at the v_fma rate)
-  static const bool dot = env_int("NIDT_C1WG_DOT", 0) == 1;
-#define NIDT_C1WG(U)                                                                                                \
-  hipLaunchKernelGGL(k_conv1_wgrad_split<U>, dim3(kPD * NB * nq), dim3(256), 0, s, ptr<const uint8_t>(x8),          \
-                     ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout), ptr<const uint8_t>(amax), \
-                     ptr<float>(part), nq)
-  static const int smf_env = env_int("NIDT_C1WG_SMF", 0);
-  // NIDT_C1WG_MX=0 falls back from the argmax-row smfmac kernel (default) to the VALU gather
-  static const int mx_env = env_int("NIDT_C1WG_MX", 1);
-  const int mode = g_c1wg_mode >= 0 ? g_c1wg_mode : (smf_env == 1 ? 1 : mx_env == 1 ? 2 : 0);
-  const bool smf = mode == 1;
+  const int mode = g_c1wg_mode >= 0 ? g_c1wg_mode : 2;
+  NIDT_REQUIRE(mode == 0 || mode == 2, "conv1_wgrad: mode must be 0 (VALU gather), 2 (smfmac) or -1 (default)");
   int nslab = B * kPD * nq;  // part slabs per client
   if (mode == 2) {
     const int npb = conv1_wgrad_mx_npb(NB), nblk = (kPD + npb - 1) / npb;
     NIDT_REQUIRE(nblk <= kPD * nq, "conv1_wgrad: part buffer");
-    static const int dbg = env_int("NIDT_C1WG_DBG", 0);
-    if (dbg)
-      hipLaunchKernelGGL(k_conv1_wgrad_mx<1>, dim3(NB * nblk), dim3(512), 0, s, ptr<const uint8_t>(x8),
-                         ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout),
-                         ptr<const uint8_t>(amax), ptr<float>(part), npb, nblk);
-    else
-      hipLaunchKernelGGL(k_conv1_wgrad_mx<0>, dim3(NB * nblk), dim3(512), 0, s, ptr<const uint8_t>(x8),
-                         ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout),
-                         ptr<const uint8_t>(amax), ptr<float>(part), npb, nblk);
+    hipLaunchKernelGGL(k_conv1_wgrad_mx, dim3(NB * nblk), dim3(512), 0, s, ptr<const uint8_t>(x8),
+                       ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout),
+                       ptr<const uint8_t>(amax), ptr<float>(part), npb, nblk);
     nslab = B * nblk;
-  } else if (smf)
-    hipLaunchKernelGGL(k_conv1_wgrad_smf, dim3(kPD * NB * nq), dim3(512), 0, s, ptr<const uint8_t>(x8),
+  } else {
+    hipLaunchKernelGGL(k_conv1_wgrad_split, dim3(kPD * NB * nq), dim3(256), 0, s, ptr<const uint8_t>(x8),
                        ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout),
                        ptr<const uint8_t>(amax), ptr<float>(part), nq);
-  else if (dot)
-    hipLaunchKernelGGL(k_conv1_wgrad_dot, dim3(kPD * NB * nq), dim3(256), 0, s, ptr<const uint8_t>(x8),
-                       ptr<const int>(idx), ptr<const uint16_t>(dp), ptr<const uint16_t>(pout),
-                       ptr<const uint8_t>(amax), ptr<float>(part), nq);
-  else if (unr == 4) NIDT_C1WG(4); else if (unr == 2) NIDT_C1WG(2); else NIDT_C1WG(1);
-#undef NIDT_C1WG
+  }
   NIDT_CHECK(hipGetLastError());
   const int G = NB / B;
   // client g's slabs are contiguous: B samples x (19 pd x nq row ranges | nblk pd ranges)

@@ -76,25 +76,18 @@ def _phases(t):
     return [r for r in range(8) if tp_valid(t, r)]
 
 
-def c1_slots(ro=0, ks=128):
+KSLOTS = 128                           # K slots of a packed conv1 weight row
+
+
+def c1_slots():
     """(tap group, phase) of every K slot of a packed conv1 weight row, None for an empty slot: the layout described
-    above c1_slot128 in conv1.hip.  ks = 224: the legacy 27 x 8 layout.  ro: the tap-group order (0 ascending, 1 and 2
-    with the two lane quarters of a read paired by jw; 2 also regroups the 2-phase groups of k-step 3)."""
-    if ks == 224:
-        return [(kk >> 3, kk & 7) if (kk >> 3) < 27 and tp_valid(kk >> 3, kk & 7) else None for kk in range(224)]
-    assert ks == 128
+    above c1_slot128 in conv1.hip (tap groups in ascending order)."""
     g = _groups()
-    pair = (lambda q: [q[0], q[2], q[1], q[3]]) if ro else (lambda q: list(q))
-    Fg = pair(g["F"][:4]) + pair(g["F"][4:])
-    Dg, Hg, Wg = pair(g["D"]), pair(g["H"]), g["W"]
-    if ro == 2:
-        x1 = [g["DW"][0], g["DW"][1], g["DHW"][0], None]
-        x2 = [g["DH"][0], g["DH"][1], g["HW"][0], g["HW"][1]]
-    else:
-        x1 = [g["DH"][0], g["DW"][0], g["HW"][0], g["DHW"][0]]
-        x2 = [g["DH"][1], g["DW"][1], g["HW"][1], None]
+    Fg, Dg, Hg, Wg = g["F"], g["D"], g["H"], g["W"]
+    x1 = [g["DH"][0], g["DW"][0], g["HW"][0], g["DHW"][0]]
+    x2 = [g["DH"][1], g["DW"][1], g["HW"][1], None]
     out = []
-    for kk in range(128):
+    for kk in range(KSLOTS):
         st, fq, e = kk >> 5, (kk >> 3) & 3, kk & 7
         if st < 2:
             t, ph = Fg[4 * st + fq], list(range(8))
@@ -110,10 +103,6 @@ def c1_slots(ro=0, ks=128):
         t = (x1 if e < 6 else x2)[fq]
         if t is None:
             out.append(None)
-            continue
-        if ro == 2 and e < 6:
-            r = (0, 2)[e & 1]             # the X1 quarter reads phases 0, 2 of its group (DHW has no phase 2)
-            out.append((t, r) if tp_valid(t, r) else None)
             continue
         ph = _phases(t)
         out.append((t, ph[e & 1]) if (e & 1) < len(ph) else None)
@@ -219,9 +208,9 @@ def conv1_pool_ref(acc, mult, shift, B):
     return z.to(torch.bfloat16), torch.stack(ams), torch.stack(mx)
 
 
-def pack_ref(c, scale_arg, ro=0, ks=128, signed=True):
-    """(w8 [G, 64, ks] int16 bit patterns of f16(sign w) per slot, w125 [G, 64, 125] = f16(w) * scale_arg in fp32)."""
-    slots = c1_slots(ro, ks)
+def pack_ref(c, scale_arg, signed=True):
+    """(w8 [G, 64, 128] int16 bit patterns of f16(sign w) per slot, w125 [G, 64, 125] = f16(w) * scale_arg in fp32)."""
+    slots, ks = c1_slots(), KSLOTS
     bits = c.w.to(torch.float16).view(torch.int16).to(torch.int32) & 0xffff
     if signed:
         bits = torch.where(c.sign.unsqueeze(2) < 0, bits ^ 0x8000, bits)

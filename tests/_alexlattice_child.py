@@ -1,19 +1,7 @@
-"""Runners of the conv1 lattice checks on the GPU (raw bindings), shared by tests/test_gpu_exact_alexnet.py and by the
-child processes it starts for the environment-selected kernel variants (the NIDT_C1* switches are read once per
-process).  As a program: ``python _alexlattice_child.py case.pt`` runs the NB = 4 forward check and the NB = 4 slab check
-on the operands and references the parent saved, with whatever variant the environment selects; it prints the
-coordinates of the first mismatch and exits non-zero."""
-import os
-import sys
-
+"""Runners of the conv1 lattice checks on the GPU (raw bindings), used by tests/test_gpu_exact_alexnet.py."""
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-for p in (HERE, os.path.dirname(HERE)):
-    if p not in sys.path:
-        sys.path.insert(0, p)
-
-import _alexlattice as A  # noqa: E402
+import _alexlattice as A
 
 DEV = "cuda"
 NAN = float("nan")
@@ -82,29 +70,3 @@ def check_slabs(part, G, nsl, S, D, what):
     assert e is None, what + " S: " + e
     e = A.first_mismatch(gd, D, ("client", "channel"))
     assert e is None, what + " D: " + e
-
-
-def main(path):
-    d = torch.load(path)
-    m = ext()
-    c = d["c"]
-    x8, idx = d["x8"].to(DEV), c["idx"].to(DEV)
-    w8, _ = run_pack(m, c["theta"].to(DEV), c["P"], c["off_w"], c["off_sign"], c["G"], 1.0 / 255.0)
-    out, amax = run_fwd(m, x8, idx, w8, c["scale"].to(DEV), c["shift"].to(DEV), c["NB"], c["B"])
-    ref = type("C", (), {"out": c["out"], "amax": c["amax"]})
-    A.check_conv1_fwd(out, amax, ref)
-    print("forward ok (kslots %d)" % m.conv1_kslots())
-    w = d["w"]
-    mode = 2 if os.environ.get("NIDT_C1WG_MX", "1") == "1" else 0
-    f = A.fin_case(c["G"], False)
-    part, _ = run_wgrad(m, x8, idx, w["dp"].to(DEV), w["pout"].to(DEV), w["amax"].to(DEV), c["NB"], c["B"], f)
-    check_slabs(part, c["G"], nslab(m, c["NB"], c["B"], mode), w["S"], w["D"], "slab sums (mode %d)" % mode)
-    print("slab sums ok (mode %d)" % mode)
-
-
-if __name__ == "__main__":
-    try:
-        main(sys.argv[1])
-    except AssertionError as e:
-        print("MISMATCH:", e)
-        sys.exit(1)

@@ -36,33 +36,24 @@ def _pool_at(h, amax):
 
 
 # ================================================================================================ conv1 layout
-@pytest.mark.parametrize("ro,ks", [(0, 128), (1, 128), (2, 128), (0, 224)])
-def test_slot_layout_covers_125_taps_once(ro, ks):
-    slots = A.c1_slots(ro, ks)
-    assert len(slots) == ks
+def test_slot_layout_covers_125_taps_once():
+    slots = A.c1_slots()
+    assert len(slots) == A.KSLOTS
     assert sorted(A.slot_taps(slots)) == list(range(125))
-    assert slots.count(None) == ks - 125
+    assert slots.count(None) == A.KSLOTS - 125
     assert all(A.tp_valid(*s) for s in slots if s is not None)
 
 
 def test_slot_layout_structure():
     """The layout as the comment above c1_slot128 states it: 8 F groups of 8 phases in k-steps 0-1, D + H groups in k-step
     2, W + the 2-phase groups in k-step 3, 3 empty slots at the end of the last lane group."""
-    s = A.c1_slots(0)
+    s = A.c1_slots()
     g = A._groups()
     assert [len(g[k]) for k in ("F", "D", "H", "W", "DH", "DW", "HW", "DHW")] == [8, 4, 4, 4, 2, 2, 2, 1]
     assert [s[8 * i][0] for i in range(8)] == g["F"]
     assert [s[64 + 8 * i][0] for i in range(4)] == g["D"] and [s[68 + 8 * i][0] for i in range(4)] == g["H"]
     assert [s[96 + 8 * i][0] for i in range(4)] == g["W"]
     assert s[125:] == [None, None, None] and s[124] == (26, 0)
-    # the paired orders keep the same groups per k-step and pair equal jw within (fq 0, fq 1) and (fq 2, fq 3)
-    for ro in (1, 2):
-        p = A.c1_slots(ro)
-        for st in range(3):
-            assert sorted(x[0] for x in p[32 * st:32 * st + 32]) == sorted(x[0] for x in s[32 * st:32 * st + 32])
-            for e in (0, 4):
-                t = [p[32 * st + 8 * fq + e][0] for fq in range(4)]
-                assert t[0] % 3 == t[1] % 3 and t[2] % 3 == t[3] % 3
 
 
 # ================================================================================================ conv1 forward
@@ -125,12 +116,10 @@ def test_pack_reference():
     w8, w125 = A.pack_ref(c, 1.0)
     assert torch.equal(w125, c.w)
     back = w8.view(torch.float16).float()
-    slots = A.c1_slots(0)
+    slots = A.c1_slots()
     for kk in (0, 37, 70, 100, 124):
         assert torch.equal(back[:, :, kk], c.w[:, :, A.tp_to_k(*slots[kk])] * c.sign)
     assert bool((w8[:, :, 125:] == 0).all())
-    w8b, _ = A.pack_ref(c, 1.0, ro=2)
-    assert not torch.equal(w8, w8b) and torch.equal(w8.sort(2)[0], w8b.sort(2)[0])
 
 
 # ================================================================================================ conv1 statistics
@@ -447,7 +436,7 @@ def test_mutation_swapped_taps_in_one_channel():
     c = A.conv1_case()
     g, ch = 0, 4                                   # a live channel of small scale (k = 10): the norm hardly sees it
     assert int(c.kexp[g, ch]) == 10 and not bool(c.dead[ch])
-    s = A.c1_slots(0)
+    s = A.c1_slots()
     k1, k2 = A.tp_to_k(*s[8]), A.tp_to_k(*s[9])                    # tap group 1, phases 0 and 1
     w = c.w.clone()
     assert w[g, ch, k1] != w[g, ch, k2]

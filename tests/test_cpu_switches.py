@@ -1,5 +1,6 @@
 """The NIDT_* environment switches the HIP sources read: conv3d.hip keeps exactly the twelve that choose between two
-surviving kernels or move a live threshold (the table of the README), and no switch is read with two defaults.
+surviving kernels or move a live threshold (the table of the README), conv1.hip reads none, and no switch is read with
+two defaults.
 
 The scan sees reads written as ``env_int("NIDT_...", <integer literal>)`` / ``env_int64(...)``, the one form the kernel
 files use (common.h); a read with another default expression, or a kernel file calling getenv itself, fails the scan
@@ -31,6 +32,10 @@ def _reads():
 
 def test_conv3d_switches_are_the_kept_table():
     assert dict(_reads()["conv3d.hip"]) == CONV3D
+
+
+def test_conv1_reads_no_switch():
+    assert _reads()["conv1.hip"] == []
 
 
 def test_no_switch_has_two_defaults():

@@ -9,8 +9,8 @@ equal accumulators the LARGEST index dd 9 + dh 3 + dw wins when acc >= 0, the sm
 takes the FIRST maximum in (d, h, w) scan order (PyTorch's rule).  The two rules differ on ties; each is pinned here.
 
 Exact (bit for bit, or equal as fp64 values): polyphase, patch moments, pack_conv1_w (w8 per slot, w125), conv1_fwd_pool in
-both modes (and the two modes against each other, ties included), the part-slab sums S / D of conv1_wgrad in modes 0, 1, 2
-at NB = 4 and NB = 256, the closed form of k_conv1_wgrad_fin (train and eval), every NIDT_C1* variant in a child process,
+both modes (and the two modes against each other, ties included), the part-slab sums S / D of conv1_wgrad in modes 0, 2
+at NB = 4 and NB = 256, the closed form of k_conv1_wgrad_fin (train and eval),
 bn_relu_pool (values and argmax), bn_relu_apply, bn_bwd sums / eval-mode dy, bn_finalize and bn_eval with eps = 0, head
 logits (eval, train, dropout), the zero-logit head gradients, cls_head_train with softmax 1 / K.
 Bounded (counted fp32 roundings, _alexlattice.py): conv1_bnstats, the running statistics, train-mode bn_bwd dy (N = B D H W
@@ -28,14 +28,10 @@ result is stored in bf16, or the bound is one fp32 rounding, the ratio sits just
           at worst over the cases (DEV_REL = 4 x 0.271); with K_HEAD = 8: dw1 0.165, db1 0.076, dw2 0.097, db2 0.030,
           dp5 0.968 (bf16), loss 0.078; under dropout dw1 0.082, dw2 0.080, dp5 0.302, loss 0.057
     cls_head_train (K = 10): dlog 0.077, dW 0.138, db 0.098, da 0.903 (bf16), lossn 0.044, losses 0.028
-Wall time of this file on an MI355X: 151 tests in 20.9 s (slowest: a variant child, 2.5 s; slowest in-process case 0.9 s);
-tests/test_gpu_kernels.py on the same machine: 122 tests in 22.1 s.
-No kernel bug found: every kernel and every variant met its exact or counted check on the first run.
+Wall time of this file on an MI355X with the six variant children it once had: 151 tests in 20.9 s (slowest in-process
+case 0.9 s); tests/test_gpu_kernels.py on the same machine: 122 tests in 22.1 s.
+No kernel bug found: every kernel met its exact or counted check on the first run.
 """
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
@@ -88,7 +84,7 @@ def test_conv1_sample_moments_exact(dev):
 
 @pytest.mark.parametrize("scale_arg", [1.0 / 255.0, 1.0])
 def test_pack_conv1_w_slots(scale_arg):
-    """w8 slot by slot against the layout's definition (default process: 128 slots, original tap order), w125 exactly."""
+    """w8 slot by slot against the layout's definition (128 slots), w125 exactly."""
     m, c = _m(), A.conv1_case()
     assert m.conv1_kslots() == 128
     w8, w125 = R.run_pack(m, c.theta.to(DEV), c.P, c.off_w, c.off_sign, c.G, scale_arg)
@@ -201,7 +197,7 @@ def _wg_dev(NB):
     return w.idx.to(DEV)[sel].contiguous(), dp, w.pout.to(DEV)[sel].contiguous(), w.amax.to(DEV)[sel].contiguous(), s
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("mode", [0, 2])
 @pytest.mark.parametrize("NB,B", [(A.C1_NB, A.C1_B), A.C1_BIG])
 def test_conv1_wgrad_slab_sums_exact(dev, NB, B, mode):
     """The per-client fp64 sum of the part slabs equals the integer reference exactly: S (125 taps) and D."""
@@ -222,7 +218,7 @@ def test_conv1_wgrad_slab_sums_exact(dev, NB, B, mode):
 
 
 @pytest.mark.parametrize("eval_mode", [False, True])
-@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("mode", [0, 2])
 def test_conv1_wgrad_closed_form_exact(dev, mode, eval_mode):
     """k_conv1_wgrad_fin on dyadic statistics: dW, dgamma, dbeta = D and dbias bit for bit, train and eval form."""
     m, w = _m(), A.wgrad_case()
@@ -241,44 +237,16 @@ def test_conv1_wgrad_closed_form_exact(dev, mode, eval_mode):
         L.assert_exact(grad[:, o:o + 64], ref[k], ("client", "channel"))
 
 
-# ================================================================================================ environment variants
-VARIANTS = [{"NIDT_C1_TAPORD": "1"}, {"NIDT_C1_TAPORD": "2"}, {"NIDT_C1_K224": "1"}, {"NIDT_C1_FWD": "0"},
-            {"NIDT_C1WG_DOT": "1", "NIDT_C1WG_MX": "0"}, {"NIDT_C1WG_UNROLL": "4", "NIDT_C1WG_MX": "0"}]
-CHILD_TIMEOUT = 10      # seconds: one measured child run takes 2.3 s (interpreter start, extension load, two checks);
-                        # 3 x that is 7 s, rounded up
-_child_fault = []       # a child that ended by signal or timeout: no further child is started
-
-
-@pytest.fixture(scope="module")
-def child_case(dev, tmp_path_factory):
-    c, w = A.conv1_case(), A.wgrad_case()
-    S, D = A.wgrad_client(w.S, w.D, w.B)
-    path = tmp_path_factory.mktemp("alexlattice") / "case.pt"
-    torch.save(dict(x8=dev["x8"].cpu(),
-                    c=dict(G=c.G, B=c.B, NB=c.NB, P=c.P, off_w=c.off_w, off_sign=c.off_sign, idx=c.idx, theta=c.theta,
-                           scale=c.scale, shift=c.shift, out=c.out, amax=c.amax),
-                    w=dict(dp=w.dp, pout=w.pout, amax=w.amax, S=S, D=D)), path)
-    return str(path)
-
-
-@pytest.mark.parametrize("env", VARIANTS, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
-def test_conv1_env_variant_in_child(child_case, env):
-    """Each opt-in variant, selected by its environment variable in a fresh child process, passes the NB = 4 forward and
-    slab checks."""
-    assert not _child_fault, "an earlier variant child ended by signal or timeout (%s): not launching" % _child_fault[0]
-    e = dict(os.environ)
-    e.update(env)
+def test_conv1_wgrad_mode_1_is_rejected(dev):
+    """Mode 1 named the removed x-ordered smfmac kernel: it fails before any launch and falls through to no other kernel."""
+    m, w = _m(), A.wgrad_case()
+    idx, dp, pout, amax, _ = _wg_dev(4)
+    m.conv1_wgrad_mode(1)
     try:
-        p = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                         "_alexlattice_child.py"), child_case],
-                           env=e, timeout=CHILD_TIMEOUT, capture_output=True, text=True)
-    except subprocess.TimeoutExpired:
-        _child_fault.append("%s: timeout" % env)
-        raise AssertionError("variant child %s did not finish in %d s" % (env, CHILD_TIMEOUT))
-    print(p.stdout[-2000:])
-    if p.returncode < 0:
-        _child_fault.append("%s: signal %d" % (env, -p.returncode))
-    assert p.returncode == 0, "variant %s: exit %d\n%s\n%s" % (env, p.returncode, p.stdout[-2000:], p.stderr[-2000:])
+        with pytest.raises(ValueError, match="conv1_wgrad: mode"):
+            R.run_wgrad(m, dev["x8"], idx, dp, pout, amax, w.NB, w.B, A.fin_case(w.G, False))
+    finally:
+        m.conv1_wgrad_mode(-1)
 
 
 # ================================================================================================ bn.hip
