@@ -1,5 +1,5 @@
-"""Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_any.hip``,
-``conv2d_wg.hip``, ``linear_g.hip``).
+"""Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_fd.hip``,
+``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``).
 
 The small models of the reference's entry points (``lenet5``, ``cnn_cifar10/100``, the EMNIST CNNs, ``vgg11/16`` —
 ``fedml_experiments/standalone/subavg/main_subavg.py:143-158``) run G clients of a lockstep step as one pass over
@@ -7,8 +7,11 @@ group-stacked tensors ``[G*B, C, H, W]``: a deep copy of the model whose ``Conv2
 modules are replaced by grouped twins reading the clients' parameter rows (``[G, *shape]`` views of theta):
 
 * ``Conv2d`` (stride 1, any kernel size and channel count) -> :class:`HipConv2dFn`: forward and stride-1 data
-  gradient on the implicit-GEMM MFMA kernel (``conv2d_any.hip``), weight and bias gradient on the MFMA kernel of
-  ``conv2d_wg.hip``, which owns each output element and writes fp32 in the parameter layout, both bf16 weight images
+  gradient on the LDS-staged MFMA kernel of ``conv2d_fd.hip`` where the contraction channel count is a multiple of 8
+  and at least 64 (``conv2d_fd_ok``; both directions read the forward weight image: no transposed image is packed
+  for such a layer), on the implicit-GEMM MFMA kernel of ``conv2d_any.hip`` otherwise (first and narrow layers) and
+  everywhere with ``NIDT_B2D_FD=0``; weight and bias gradient on the MFMA kernel of
+  ``conv2d_wg.hip``, which owns each output element and writes fp32 in the parameter layout, the bf16 weight images
   from one ``conv2d_pack_w`` launch; ``NIDT_B2D_WGRAD=0`` keeps the staged fp32 weight-gradient kernel of
   ``conv2d_any.hip`` with its framework partial sum, bias sum and packing; the activations stay channels-last
   (``torch.channels_last`` views), bf16;
@@ -94,6 +97,48 @@ def conv2d_wg_ok(k, Wo, G, cin, cout):
     return k <= 7 and conv2d_wg_lds_bytes(k, Wo, cin) <= 65536 and blocks >= WG_MIN_BLOCKS
 
 
+def _hip_fd_on():
+    return os.environ.get("NIDT_B2D_FD", "1") != "0"
+
+
+def conv2d_fd_lds_bytes(k, Wo):
+    """The dynamic LDS of a ``conv2d_fd`` launch that writes a ``Wo``-wide map: the launcher's own arithmetic (two
+    64 x 72 bf16 weight tiles and ``nu`` union rows of 72, nu = 64 + (k - 1) min(64, 1 + ceil(63 / Wo)))."""
+    nu = 64 + (k - 1) * min(64, 1 + (63 + Wo - 1) // Wo)
+    return 2 * 72 * (2 * 64 + nu)
+
+
+FD_MIN_C = 64
+
+
+def conv2d_fd_served(k, pad, W, cin, cout, dgrad):
+    """The launcher's rule for a layer described by its forward (input width ``W``): kernels up to 7 x 7, the
+    contraction channel count (cin forward, cout data gradient; its stride is the same number here) a multiple of 8,
+    padding within the kernel for the data gradient, LDS within 64 KiB for the width of the map written."""
+    Wo = W if dgrad else W + 2 * pad - k + 1
+    return (1 <= k <= 7 and (cout if dgrad else cin) % 8 == 0 and pad >= 0 and (pad <= k - 1 or not dgrad)
+            and Wo > 0 and conv2d_fd_lds_bytes(k, Wo) <= 65536)
+
+
+def conv2d_fd_ok(k, pad, W, cin, cout, dgrad):
+    """The layers whose forward / data gradient runs on ``conv2d_fd``; everything else keeps ``conv2d_any_fwd``.
+
+    * the launcher's rule (``conv2d_fd_served``);
+    * the measured rule (``profiles/r13_conv2d_fd.txt``): at least ``FD_MIN_C`` contraction channels.  A step of the
+      kernel is one tap of one 64-channel chunk, in 32-deep MFMAs, behind a barrier; with 16 channels every MFMA is
+      half padding and a 5 x 5 kernel takes 25 such steps where the old kernel walks the 400-long contraction in 13
+      unsynchronised ones: LeNet5_cifar's 6 -> 16 data gradient ran at 0.45x / 0.42x of the old kernel (100 x 16 /
+      8 x 64).  With 32 channels (the EMNIST CNNs' 32 -> 64 forward) a step issues half its MFMAs per barrier:
+      0.88x / 0.85x at k = 5, 1.00x / 0.98x at k = 3.  Every launch measured with 64 or more contraction channels
+      was faster, 1.58x - 2.96x forward and 1.81x - 2.98x for the data gradient with its pack, against a run-to-run
+      spread of 1 - 3 percent.  Nothing was measured at 40 .. 56 channels; they stay on the old kernel."""
+    return conv2d_fd_served(k, pad, W, cin, cout, dgrad) and (cout if dgrad else cin) >= FD_MIN_C
+
+
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _client_blocks(w):
     """w [G, ...] as (tensor whose clients are contiguous blocks at one stride, that stride in elements)."""
     if not (w.dtype == torch.float32 and w[0].is_contiguous() and (w.shape[0] == 1 or w.stride(0) >= w[0].numel())):
@@ -118,7 +163,9 @@ class HipConv2dFn(torch.autograd.Function):
     """Grouped stride-1 conv: x [G*B, Cin, H, W] (any strides), w [G, Cout, Cin, k, k] fp32, b [G, Cout] or None.
     With ``NIDT_B2D_WGRAD=1`` (the default) the weight images come from ``conv2d_pack_w`` and the weight / bias
     gradients from ``conv2d_wg`` (``conv2d_wg.hip``), in the parameter layout; 0 keeps the framework packing and
-    ``conv2d_any_wgrad`` with its partial sums."""
+    ``conv2d_any_wgrad`` with its partial sums.  With ``NIDT_B2D_FD=1`` (the default) the forward and the data
+    gradient of the layers ``conv2d_fd_ok`` accepts run on ``conv2d_fd`` (``conv2d_fd.hip``); the data gradient then
+    reads the saved forward image and no transposed image is packed; 0 keeps ``conv2d_any_fwd`` for both."""
 
     @staticmethod
     def forward(ctx, x, w, b, G, pad):
@@ -131,22 +178,29 @@ class HipConv2dFn(torch.autograd.Function):
         Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
         y = torch.empty(N, Ho, Wo, co, device=x.device, dtype=torch.bfloat16)
         ctx.new = _hip_wgrad_on()
+        fd = _hip_fd_on()
+        ctx.fd_d = fd and ctx.needs_input_grad[0] and conv2d_fd_ok(k, pad, W, ci, co, True)
         wt = None
         if ctx.new:
-            wp, wt = pack_conv_images(w.detach(), ctx.needs_input_grad[0])
+            wp, wt = pack_conv_images(w.detach(), ctx.needs_input_grad[0] and not ctx.fd_d)
         else:
             wp = pack_conv_w(w.detach())
         bias = b.detach().float().contiguous() if b is not None else None
-        m.conv2d_any_fwd(xs.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else 0, y.data_ptr(), G, B,
-                         H, W, ci, ci, co, k, pad, _stream())
-        ctx.save_for_backward(xs, w, wt)
+        if fd and conv2d_fd_ok(k, pad, W, ci, co, False):
+            xs = _aligned16(xs)
+            m.conv2d_fd(xs.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else 0, y.data_ptr(), G, B,
+                        H, W, ci, ci, co, k, pad, 0, _stream())
+        else:
+            m.conv2d_any_fwd(xs.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else 0, y.data_ptr(),
+                             G, B, H, W, ci, ci, co, k, pad, _stream())
+        ctx.save_for_backward(xs, w, wp if ctx.fd_d else wt)  # the data gradient on conv2d_fd reads the forward image
         ctx.G, ctx.pad, ctx.has_b = G, pad, b is not None
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
         m = ops.ext()
-        xs, w, wt = ctx.saved_tensors
+        xs, w, wt = ctx.saved_tensors  # wt: the forward image when ctx.fd_d, else the transposed image or None
         G, pad = ctx.G, ctx.pad
         N, H, W, ci = xs.shape
         co, k = w.shape[1], w.shape[3]
@@ -155,11 +209,16 @@ class HipConv2dFn(torch.autograd.Function):
         Ho, Wo = dy.shape[1], dy.shape[2]
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            if wt is None:
-                wt = pack_conv_wt(w.detach())
             dxs = torch.empty(N, H, W, ci, device=xs.device, dtype=torch.bfloat16)
-            m.conv2d_any_fwd(dy.data_ptr(), wt.data_ptr(), 0, dxs.data_ptr(), G, B, Ho, Wo, co, co, ci, k, k - 1 - pad,
-                             _stream())
+            if ctx.fd_d:
+                dy = _aligned16(dy)
+                m.conv2d_fd(dy.data_ptr(), wt.data_ptr(), 0, dxs.data_ptr(), G, B, H, W, ci, co, co, k, pad, 1,
+                            _stream())
+            else:
+                if wt is None:
+                    wt = pack_conv_wt(w.detach())
+                m.conv2d_any_fwd(dy.data_ptr(), wt.data_ptr(), 0, dxs.data_ptr(), G, B, Ho, Wo, co, co, ci, k,
+                                 k - 1 - pad, _stream())
             dx = dxs.permute(0, 3, 1, 2)
         want_b = ctx.has_b and ctx.needs_input_grad[2]
         if ctx.new and conv2d_wg_ok(k, Wo, G, ci, co):
