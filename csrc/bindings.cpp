@@ -145,6 +145,13 @@ void gn_bwd(uintptr_t dy, int dy_bf16, uintptr_t mask, uintptr_t t, uintptr_t st
             int64_t off_w, uintptr_t dt, uintptr_t part, int N, int B, int S, int C, uintptr_t stream);
 void gn_param_grads(uintptr_t part, int G, int B, int C, uintptr_t grads, int64_t ldg, int64_t off_w, int64_t off_b,
                     uintptr_t stream);
+// gn_pool.hip
+void gn2d_fwd(uintptr_t t, uintptr_t gamma, uintptr_t beta, int64_t ld, uintptr_t y, uintptr_t stats, int N, int B,
+              int H, int W, int C, int groups, float eps, int relu, int pool, uintptr_t stream);
+void gn2d_bwd(uintptr_t dy, uintptr_t t, uintptr_t stats, uintptr_t gamma, uintptr_t beta, int64_t ld, uintptr_t dt,
+              uintptr_t part, int N, int B, int H, int W, int C, int groups, int relu, int pool, uintptr_t stream);
+void pool2d_fwd(uintptr_t x, uintptr_t y, int N, int H, int W, int C, uintptr_t stream);
+void pool2d_bwd(uintptr_t dy, uintptr_t x, uintptr_t dx, int N, int H, int W, int C, uintptr_t stream);
 void res_grad(uintptr_t out, uintptr_t dx1, uintptr_t dx2, uintptr_t da, uintptr_t mask, int64_t n, int flags,
               uintptr_t stream);
 void res_grad_s2(uintptr_t out, uintptr_t dx1, uintptr_t dx2s, int N, int D, int H, int W, int C, int out_bf16,
@@ -377,6 +384,10 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(gn_bwd_rm);
   DEF(gn_rm_ok);
   DEF(gn_param_grads);
+  DEF(gn2d_fwd);
+  DEF(gn2d_bwd);
+  DEF(pool2d_fwd);
+  DEF(pool2d_bwd);
   DEF(res_grad_om);
   DEF(res_grad_s2_om);
   DEF(res_grad);

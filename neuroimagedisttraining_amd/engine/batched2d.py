@@ -97,7 +97,8 @@ class BatchedModuleEngine:
                        / torch.tensor(std, dtype=torch.float32, device=self.device)).view(1, c, 1, 1)
         self._opt = None
         # GPU: the hand-written grouped layers (conv2d_hip.py: conv2d_any.hip convolutions, linear_g.hip linears on
-        # the fp32 rows in place, grouped GroupNorm) over group-stacked tensors instead of vmapped library calls;
+        # the fp32 rows in place, GroupNorm + ReLU + 2x2 max-pool and the lone 2x2 pools on gn_pool.hip) over
+        # group-stacked tensors instead of vmapped library calls;
         # NIDT_B2D_HIP=0 keeps the vmap path (the CPU always uses it)
         self._grouped = None
         if self.device.type == "cuda" and os.environ.get("NIDT_B2D_HIP", "1") != "0":

@@ -1,10 +1,10 @@
 """Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_fd.hip``,
-``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``).
+``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``, ``gn_pool.hip``).
 
 The small models of the reference's entry points (``lenet5``, ``cnn_cifar10/100``, the EMNIST CNNs, ``vgg11/16`` —
 ``fedml_experiments/standalone/subavg/main_subavg.py:143-158``) run G clients of a lockstep step as one pass over
-group-stacked tensors ``[G*B, C, H, W]``: a deep copy of the model whose ``Conv2d`` / ``Linear`` / ``GroupNorm``
-modules are replaced by grouped twins reading the clients' parameter rows (``[G, *shape]`` views of theta):
+group-stacked tensors ``[G*B, C, H, W]``: a deep copy of the model whose ``Conv2d`` / ``Linear`` / ``GroupNorm`` /
+``MaxPool2d(2, 2)`` modules are replaced by grouped twins reading the clients' parameter rows (``[G, *shape]`` views of theta):
 
 * ``Conv2d`` (stride 1, any kernel size and channel count) -> :class:`HipConv2dFn`: forward and stride-1 data
   gradient on the LDS-staged MFMA kernel of ``conv2d_fd.hip`` where the contraction channel count is a multiple of 8
@@ -19,8 +19,15 @@ modules are replaced by grouped twins reading the clients' parameter rows (``[G,
   ``linear_g.hip``, which read the fp32 weight rows in place (rounded to bf16 in registers, no bf16 weight copy) and
   write fp32-accumulated fp32 weight gradients in a fixed order; ``NIDT_B2D_LINEAR=0`` (and the CPU) keeps one
   batched library GEMM per layer (``baddbmm`` over the client axis);
-* ``GroupNorm`` -> ``group_norm`` without affine on the stacked batch, then the per-client affine;
-* everything else (ReLU, max-pool, dropout, flatten) is per-sample and runs unchanged on the stacked batch.
+* ``GroupNorm`` and, inside an ``nn.Sequential``, the ``ReLU`` and the ``MaxPool2d(2, 2)`` that follow it ->
+  :class:`HipGroupNormFn`: one forward and one backward kernel of ``gn_pool.hip`` over the channels-last bf16
+  activation, the per-client affine read from the parameter rows in place, the ReLU mask and the pooling argmax
+  recomputed in the backward (no mask or index tensor); the absorbed modules become ``nn.Identity`` at their
+  indices.  A ``MaxPool2d(2, 2)`` on its own -> :class:`HipMaxPool2dFn` (same file).  ``NIDT_B2D_GN=0``, the CPU and
+  the shapes outside ``gn2d_ok`` / ``pool2d_ok`` run the framework expression (``group_norm`` without affine, the
+  per-client affine, ``relu``, ``max_pool2d``);
+* everything else (other ReLUs, dropout, flatten, functional pooling) is per-sample and runs unchanged on the
+  stacked batch.
 
 The model's own ``forward`` runs as written, so the layer order and every view/flatten are the reference's.
 """
@@ -345,22 +352,140 @@ class GLinear(nn.Module):
         return y.reshape(x.shape[0], w.shape[1])
 
 
+def _hip_gn_on():
+    return os.environ.get("NIDT_B2D_GN", "1") != "0"
+
+
+def gn2d_ok(H, W, C, groups, pool):
+    """The launcher's rule of ``gn2d_fwd`` / ``gn2d_bwd``: C / 8 a power of two up to 64, channels per group dividing
+    8 or a multiple of 8, a register-resident sample (H W C <= 65536), even H and W under the pool."""
+    nch = C // 8
+    if C % 8 or nch < 1 or nch > 64 or nch & (nch - 1) or groups < 1 or C % groups:
+        return False
+    cg = C // groups
+    return (8 % cg == 0 or cg % 8 == 0) and 0 < H * W * C <= 65536 and not (pool and (H % 2 or W % 2))
+
+
+def pool2d_ok(H, W, C):
+    """The launcher's rule of ``pool2d_fwd`` / ``pool2d_bwd``.  No measured rule on top of it
+    (``profiles/r14_gn_pool.txt``): cnn_cifar10's 28 x 28 pool ran 3.9x / 1.28x faster forward + backward (100 x 16 /
+    8 x 64); its 10 x 10 pool is launch-bound on both paths (about 0.02 ms forward) and the Python autograd function
+    costs more host time than the framework op there, 0.76x at both sizes, yet the cnn_cifar10 step with both pools
+    routed here took 0.861 / 0.964 of the step with ``NIDT_B2D_GN=0``."""
+    return C % 8 == 0 and H % 2 == 0 and W % 2 == 0 and H > 0 and W > 0
+
+
+def _affine_rows(gamma, beta):
+    """gamma, beta [G, C] as fp32 tensors with unit channel stride and one common client stride (the views of the
+    parameter rows are that already), and the stride."""
+    ok = lambda a: a.dtype == torch.float32 and a.stride(1) == 1  # noqa: E731
+    if not (ok(gamma) and ok(beta) and (gamma.shape[0] == 1 or gamma.stride(0) == beta.stride(0))):
+        gamma, beta = gamma.float().contiguous(), beta.float().contiguous()
+    return gamma, beta, (gamma.stride(0) if gamma.shape[0] > 1 else gamma.shape[1])
+
+
+class HipGroupNormFn(torch.autograd.Function):
+    """GroupNorm with a per-client affine, optional ReLU and optional 2 x 2 max-pool on ``gn_pool.hip``:
+    x [G*B, C, H, W] (any strides), gamma / beta the [G, C] fp32 views of the clients' rows.  Returns the bf16
+    channels-last result as an NCHW view; the backward gives bf16 dx and fp32 dgamma / dbeta (the per-sample
+    partials summed over each client's samples in a fixed order by ``gn_param_grads``)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, G, groups, eps, relu, pool):
+        m = ops.ext()
+        N, C, H, W = x.shape
+        assert N % G == 0 and gamma.shape == (G, C) and beta.shape == (G, C)
+        xs = _aligned16(_nhwc_bf16(x))
+        ga, be, ld = _affine_rows(gamma.detach(), beta.detach())
+        y = torch.empty((N, H // 2, W // 2, C) if pool else (N, H, W, C), device=x.device, dtype=torch.bfloat16)
+        train = any(ctx.needs_input_grad[:3])
+        stats = torch.empty(N, groups, 2, device=x.device, dtype=torch.float32) if train else None
+        m.gn2d_fwd(xs.data_ptr(), ga.data_ptr(), be.data_ptr(), ld, y.data_ptr(), stats.data_ptr() if train else 0, N,
+                   N // G, H, W, C, groups, float(eps), int(relu), int(pool), _stream())
+        if train:
+            ctx.save_for_backward(xs, stats, ga, be)
+        ctx.cfg = (G, groups, ld, int(relu), int(pool))
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        m = ops.ext()
+        xs, stats, ga, be = ctx.saved_tensors
+        G, groups, ld, relu, pool = ctx.cfg
+        N, H, W, C = xs.shape
+        dy = _aligned16(_nhwc_bf16(gy))
+        dt = torch.empty_like(xs)
+        part = torch.empty(N, C, 2, device=xs.device, dtype=torch.float32)
+        m.gn2d_bwd(dy.data_ptr(), xs.data_ptr(), stats.data_ptr(), ga.data_ptr(), be.data_ptr(), ld, dt.data_ptr(),
+                   part.data_ptr(), N, N // G, H, W, C, groups, relu, pool, _stream())
+        gr = torch.empty(G, 2, C, device=xs.device, dtype=torch.float32)  # (dgamma, dbeta) of each client
+        m.gn_param_grads(part.data_ptr(), G, N // G, C, gr.data_ptr(), 2 * C, 0, C, _stream())
+        return dt.permute(0, 3, 1, 2), gr[:, 0], gr[:, 1], None, None, None, None, None
+
+
+class HipMaxPool2dFn(torch.autograd.Function):
+    """2 x 2 stride-2 max-pool on ``gn_pool.hip``: x [N, C, H, W] (any strides) -> bf16 channels-last result as an
+    NCHW view; the backward recomputes the argmax from the saved input (first maximum in (row, column) order)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        N, C, H, W = x.shape
+        xs = _aligned16(_nhwc_bf16(x))
+        y = torch.empty(N, H // 2, W // 2, C, device=x.device, dtype=torch.bfloat16)
+        ops.ext().pool2d_fwd(xs.data_ptr(), y.data_ptr(), N, H, W, C, _stream())
+        ctx.save_for_backward(xs)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xs, = ctx.saved_tensors
+        N, H, W, C = xs.shape
+        dy = _aligned16(_nhwc_bf16(gy))
+        dx = torch.empty_like(xs)
+        ops.ext().pool2d_bwd(dy.data_ptr(), xs.data_ptr(), dx.data_ptr(), N, H, W, C, _stream())
+        return dx.permute(0, 3, 1, 2)
+
+
 class GGroupNorm(nn.Module):
-    def __init__(self, mod, name, grp):
+    """GroupNorm twin; ``relu`` / ``pool``: the ReLU (an ``nn.ReLU``, kept for its ``inplace``) and the
+    ``MaxPool2d(2, 2)`` that ``grouped_model`` absorbed into it."""
+
+    def __init__(self, mod, name, grp, relu=None, pool=False):
         super().__init__()
         self.name, self.grp = name, grp
         self.num_groups, self.eps, self.affine = mod.num_groups, mod.eps, mod.affine
+        self.relu, self.relu_inplace, self.pool = relu is not None, bool(relu is not None and relu.inplace), bool(pool)
 
     def forward(self, x):
         G = self.grp.G
-        y = F.group_norm(x, self.num_groups, None, None, self.eps)
-        if not self.affine:
-            return y
         P = self.grp.params
-        N, C = y.shape[:2]
-        w = P[self.name + ".weight"].view((G, 1, C) + (1,) * (y.dim() - 2))
-        b = P[self.name + ".bias"].view((G, 1, C) + (1,) * (y.dim() - 2))
-        return (y.view((G, N // G) + tuple(y.shape[1:])) * w + b).view(y.shape)
+        if x.is_cuda and self.affine and x.dim() == 4 and _hip_gn_on() and \
+                gn2d_ok(x.shape[2], x.shape[3], x.shape[1], self.num_groups, self.pool):
+            return HipGroupNormFn.apply(x, P[self.name + ".weight"], P[self.name + ".bias"], G, self.num_groups,
+                                        self.eps, self.relu, self.pool)
+        y = F.group_norm(x, self.num_groups, None, None, self.eps)
+        if self.affine:
+            N, C = y.shape[:2]
+            w = P[self.name + ".weight"].view((G, 1, C) + (1,) * (y.dim() - 2))
+            b = P[self.name + ".bias"].view((G, 1, C) + (1,) * (y.dim() - 2))
+            y = (y.view((G, N // G) + tuple(y.shape[1:])) * w + b).view(y.shape)
+        if self.relu:
+            y = F.relu(y, inplace=self.relu_inplace)
+        return F.max_pool2d(y, 2, 2) if self.pool else y
+
+
+class GMaxPool2d(nn.Module):
+    def forward(self, x):
+        if x.is_cuda and x.dim() == 4 and _hip_gn_on() and pool2d_ok(x.shape[2], x.shape[3], x.shape[1]):
+            return HipMaxPool2dFn.apply(x)
+        return F.max_pool2d(x, 2, 2)
+
+
+def _pool22(mod):
+    """An ``nn.MaxPool2d(2, 2)`` with padding 0, dilation 1, no ``ceil_mode`` and no indices."""
+    pair = lambda v, a: v == a or v == (a, a)  # noqa: E731
+    return (isinstance(mod, nn.MaxPool2d) and pair(mod.kernel_size, 2) and pair(mod.stride, 2)
+            and pair(mod.padding, 0) and pair(mod.dilation, 1) and not mod.ceil_mode and not mod.return_indices)
 
 
 _SWAP = {nn.Conv2d: GConv2d, nn.Linear: GLinear, nn.GroupNorm: GGroupNorm}
@@ -385,11 +510,24 @@ def grouped_model(model):
     gm = copy.deepcopy(model)
 
     def swap(parent, prefix):
-        for cname, child in list(parent.named_children()):
+        kids = list(parent.named_children())
+        absorbed = set()
+        for i, (cname, child) in enumerate(kids):
             full = prefix + cname
             cls = _SWAP.get(type(child))
-            if cls is not None:
+            if cname in absorbed:  # a ReLU / MaxPool2d that the GroupNorm before it runs: the index stays
+                setattr(parent, cname, nn.Identity())
+            elif cls is GGroupNorm:
+                relu, pool = None, False
+                if isinstance(parent, nn.Sequential) and i + 1 < len(kids) and type(kids[i + 1][1]) is nn.ReLU:
+                    relu = kids[i + 1][1]
+                    pool = i + 2 < len(kids) and _pool22(kids[i + 2][1])
+                    absorbed.update(k for k, _ in kids[i + 1:i + 3 if pool else i + 2])
+                setattr(parent, cname, GGroupNorm(child, full, grp, relu, pool))
+            elif cls is not None:
                 setattr(parent, cname, cls(child, full, grp))
+            elif _pool22(child):
+                setattr(parent, cname, GMaxPool2d())
             else:
                 swap(child, full + ".")
     swap(gm, "")
