@@ -247,6 +247,12 @@ void conv2d_pack_w(uintptr_t w, int64_t ldw, uintptr_t img, uintptr_t imgt, int 
                    uintptr_t stream);
 void conv2d_fd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int G, int B, int H, int W, int cin, int cs,
                int cout, int k, int pad, int dgrad, uintptr_t stream);
+void conv2d_thin_fwd(uintptr_t x, uintptr_t w, int64_t ldw, uintptr_t bias, int64_t ldb, uintptr_t y, int G, int B,
+                     int H, int W, int cin, int cs, int cout, int k, int pad, uintptr_t stream);
+int conv2d_thin_splits(int G, int B, int Ho, int Wo, int cout, int splits);
+void conv2d_thin_wgrad(uintptr_t x, uintptr_t dy, uintptr_t dw, int64_t lddw, uintptr_t db, int64_t lddb,
+                       uintptr_t part, int64_t part_floats, int splits, int G, int B, int H, int W, int cin, int cs,
+                       int cout, int k, int pad, uintptr_t stream);
 void linear_g_fwd(uintptr_t x, uintptr_t w, int64_t ldw, uintptr_t bias, int64_t ldb, uintptr_t y, int G, int B, int K,
                   int N, uintptr_t stream);
 void linear_g_dgrad(uintptr_t dy, uintptr_t w, int64_t ldw, uintptr_t dx, int G, int B, int K, int N,
@@ -434,6 +440,9 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(conv2d_wg);
   DEF(conv2d_pack_w);
   DEF(conv2d_fd);
+  DEF(conv2d_thin_fwd);
+  DEF(conv2d_thin_splits);
+  DEF(conv2d_thin_wgrad);
   DEF(linear_g_fwd);
   DEF(linear_g_dgrad);
   DEF(linear_g_wgrad);

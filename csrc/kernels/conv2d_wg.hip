@@ -30,7 +30,8 @@
 //  * dB: the ci-tile-0 / kh-0 blocks sum the columns of their staged dY tiles in fp32, positions ascending;
 //  * stores: a lane's k kw values of one (co, ci) are consecutive floats of the parameter layout (dword stores).
 // Few clients with a long contraction (G = 8, 28 x 28 maps: M = 50 176 -> 1568 serial steps per block) stay
-// latency-bound; a fixed-order split over positions is out of scope here, as in linear_g.hip.
+// latency-bound; a fixed-order split over positions is out of scope here, as in linear_g.hip.  The thin first layers
+// (Cin <= 4) have one: conv2d_thin.hip's k_conv2d_thin_wgrad, which conv2d_hip.py routes them to.
 // LDS: 2 x (32 x 72 + nu x (ci tile + 8)) bf16, nu = 32 + (k - 1) min(32, 1 + ceil(31 / Wo)) union rows; the launcher
 // refuses shapes above 64 KiB (of k <= 7 only the 64-wide tile at k = 7 on 1-wide maps: 73 728 B; k = 6 there takes
 // 64 512 B); conv2d_hip.py conv2d_wg_lds_bytes repeats this arithmetic.

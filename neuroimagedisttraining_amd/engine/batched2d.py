@@ -96,9 +96,9 @@ class BatchedModuleEngine:
         self._shift = (-torch.tensor(mean, dtype=torch.float32, device=self.device)
                        / torch.tensor(std, dtype=torch.float32, device=self.device)).view(1, c, 1, 1)
         self._opt = None
-        # GPU: the hand-written grouped layers (conv2d_hip.py: conv2d_any.hip convolutions, linear_g.hip linears on
-        # the fp32 rows in place, GroupNorm + ReLU + 2x2 max-pool and the lone 2x2 pools on gn_pool.hip) over
-        # group-stacked tensors instead of vmapped library calls;
+        # GPU: the hand-written grouped layers (conv2d_hip.py: conv2d_fd.hip / conv2d_thin.hip / conv2d_any.hip
+        # convolutions, linear_g.hip linears on the fp32 rows in place, GroupNorm + ReLU + 2x2 max-pool and the lone
+        # 2x2 pools on gn_pool.hip) over group-stacked tensors instead of vmapped library calls;
         # NIDT_B2D_HIP=0 keeps the vmap path (the CPU always uses it)
         self._grouped = None
         if self.device.type == "cuda" and os.environ.get("NIDT_B2D_HIP", "1") != "0":

@@ -1,5 +1,5 @@
 """Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_fd.hip``,
-``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``, ``gn_pool.hip``).
+``conv2d_thin.hip``, ``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``, ``gn_pool.hip``).
 
 The small models of the reference's entry points (``lenet5``, ``cnn_cifar10/100``, the EMNIST CNNs, ``vgg11/16`` —
 ``fedml_experiments/standalone/subavg/main_subavg.py:143-158``) run G clients of a lockstep step as one pass over
@@ -9,9 +9,12 @@ group-stacked tensors ``[G*B, C, H, W]``: a deep copy of the model whose ``Conv2
 * ``Conv2d`` (stride 1, any kernel size and channel count) -> :class:`HipConv2dFn`: forward and stride-1 data
   gradient on the LDS-staged MFMA kernel of ``conv2d_fd.hip`` where the contraction channel count is a multiple of 8
   and at least 64 (``conv2d_fd_ok``; both directions read the forward weight image: no transposed image is packed
-  for such a layer), on the implicit-GEMM MFMA kernel of ``conv2d_any.hip`` otherwise (first and narrow layers) and
-  everywhere with ``NIDT_B2D_FD=0``; weight and bias gradient on the MFMA kernel of
-  ``conv2d_wg.hip``, which owns each output element and writes fp32 in the parameter layout, the bf16 weight images
+  for such a layer), on the implicit-GEMM MFMA kernel of ``conv2d_any.hip`` otherwise (narrow layers) and
+  everywhere with ``NIDT_B2D_FD=0``; the thin first layers (at most 4 input channels, ``conv2d_thin_ok``) run their
+  forward and their weight / bias gradient on ``conv2d_thin.hip`` (a dense contraction over k k Cin, the fp32
+  weights read in place with no image packed, the gradient split over positions and summed in a fixed order;
+  ``NIDT_B2D_THIN=0`` routes them as every other layer); weight and bias gradient of the other layers on the MFMA
+  kernel of ``conv2d_wg.hip``, which owns each output element and writes fp32 in the parameter layout, the bf16 weight images
   from one ``conv2d_pack_w`` launch; ``NIDT_B2D_WGRAD=0`` keeps the staged fp32 weight-gradient kernel of
   ``conv2d_any.hip`` with its framework partial sum, bias sum and packing; the activations stay channels-last
   (``torch.channels_last`` views), bf16;
@@ -142,6 +145,41 @@ def conv2d_fd_ok(k, pad, W, cin, cout, dgrad):
     return conv2d_fd_served(k, pad, W, cin, cout, dgrad) and (cout if dgrad else cin) >= FD_MIN_C
 
 
+def _hip_thin_on():
+    return os.environ.get("NIDT_B2D_THIN", "1") != "0"
+
+
+def conv2d_thin_kp(k, cin):
+    """The padded dense contraction of ``conv2d_thin.hip``: k k cin rounded up to 32."""
+    return (k * k * cin + 31) // 32 * 32
+
+
+def conv2d_thin_served(k, cin):
+    """The launcher's rule of ``conv2d_thin_fwd`` / ``conv2d_thin_wgrad``: at most 4 input channels, kernels up to
+    7 x 7, a padded contraction of at most 96 (k = 7 only with one channel, k = 5 with up to three)."""
+    return 1 <= k <= 7 and 1 <= cin <= 4 and conv2d_thin_kp(k, cin) <= 96
+
+
+def conv2d_thin_ok(k, cin, cout):
+    """The layers whose forward and weight / bias gradient run on ``conv2d_thin.hip`` (the first layers, Cin = 1 or
+    3): the launcher's rule (``conv2d_thin_served``) alone.  The measurements add no rule
+    (``profiles/r15_conv2d_thin.txt``): the six first layers of the zoo and of the EMNIST CNNs (1->20, 3->6, 3->64,
+    1->32 at k = 5, 3->64 and 1->32 at k = 3) all beat the parent's routed paths at 100 clients x 16 images and at
+    8 x 64, by far more than the 1 - 4 percent [min .. max] spread of those paths: the forward 1.28x - 2.49x and
+    1.18x - 2.26x against ``conv2d_pack_w`` + ``conv2d_any_fwd``, the weight + bias gradient 2.93x - 4.85x against
+    ``conv2d_wg`` and 14.9x - 35x against the staged fp32 kernel that ``WG_MIN_BLOCKS`` routes to at 8 x 64.  Other
+    Cout, kernel sizes 1, 2, 4, 6, 7 and Cin = 2, 4 were not timed."""
+    return conv2d_thin_served(k, cin)
+
+
+def conv2d_thin_scratch(G, B, Ho, Wo, cout, k, cin, device, splits=0):
+    """The fp32 scratch of a ``conv2d_thin_wgrad`` launch: one 64 x Kp dW partial and 64 dB partials per (client, co
+    tile, position split), the number of splits from ``conv2d_thin_splits`` (a function of the shapes alone)."""
+    S = ops.ext().conv2d_thin_splits(G, B, Ho, Wo, cout, splits)
+    return torch.empty(G * ((cout + 63) // 64) * S * 64 * (conv2d_thin_kp(k, cin) + 1), device=device,
+                       dtype=torch.float32)
+
+
 def _aligned16(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
@@ -172,7 +210,10 @@ class HipConv2dFn(torch.autograd.Function):
     gradients from ``conv2d_wg`` (``conv2d_wg.hip``), in the parameter layout; 0 keeps the framework packing and
     ``conv2d_any_wgrad`` with its partial sums.  With ``NIDT_B2D_FD=1`` (the default) the forward and the data
     gradient of the layers ``conv2d_fd_ok`` accepts run on ``conv2d_fd`` (``conv2d_fd.hip``); the data gradient then
-    reads the saved forward image and no transposed image is packed; 0 keeps ``conv2d_any_fwd`` for both."""
+    reads the saved forward image and no transposed image is packed; 0 keeps ``conv2d_any_fwd`` for both.  With
+    ``NIDT_B2D_THIN=1`` (the default) a layer that ``conv2d_thin_ok`` accepts runs its forward on ``conv2d_thin_fwd``
+    (whatever the other two switches say: no image is packed) and, with ``NIDT_B2D_WGRAD=1``, its weight / bias
+    gradient on ``conv2d_thin_wgrad``; its data gradient (tests only) stays on ``conv2d_any_fwd``."""
 
     @staticmethod
     def forward(ctx, x, w, b, G, pad):
@@ -185,6 +226,16 @@ class HipConv2dFn(torch.autograd.Function):
         Ho, Wo = H + 2 * pad - k + 1, W + 2 * pad - k + 1
         y = torch.empty(N, Ho, Wo, co, device=x.device, dtype=torch.bfloat16)
         ctx.new = _hip_wgrad_on()
+        ctx.thin = _hip_thin_on() and conv2d_thin_ok(k, ci, co)
+        ctx.G, ctx.pad, ctx.has_b = G, pad, b is not None
+        if ctx.thin:  # the fp32 weights and bias read where they lie: no image, no pack launch
+            wb, ldw = _client_blocks(w.detach())
+            bb, ldb = _client_blocks(b.detach()) if b is not None else (None, 0)
+            m.conv2d_thin_fwd(xs.data_ptr(), wb.data_ptr(), ldw, bb.data_ptr() if b is not None else 0, ldb,
+                              y.data_ptr(), G, B, H, W, ci, ci, co, k, pad, _stream())
+            ctx.fd_d = False  # a data gradient (tests only) packs its transposed image in the backward
+            ctx.save_for_backward(xs, w, None)
+            return y.permute(0, 3, 1, 2)
         fd = _hip_fd_on()
         ctx.fd_d = fd and ctx.needs_input_grad[0] and conv2d_fd_ok(k, pad, W, ci, co, True)
         wt = None
@@ -201,7 +252,6 @@ class HipConv2dFn(torch.autograd.Function):
             m.conv2d_any_fwd(xs.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else 0, y.data_ptr(),
                              G, B, H, W, ci, ci, co, k, pad, _stream())
         ctx.save_for_backward(xs, w, wp if ctx.fd_d else wt)  # the data gradient on conv2d_fd reads the forward image
-        ctx.G, ctx.pad, ctx.has_b = G, pad, b is not None
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
@@ -228,6 +278,16 @@ class HipConv2dFn(torch.autograd.Function):
                                  k - 1 - pad, _stream())
             dx = dxs.permute(0, 3, 1, 2)
         want_b = ctx.has_b and ctx.needs_input_grad[2]
+        if ctx.new and ctx.thin:
+            if ctx.needs_input_grad[1] or want_b:
+                dw = torch.empty(G, co, ci, k, k, device=xs.device, dtype=torch.float32)
+                if want_b:
+                    db = torch.empty(G, co, device=xs.device, dtype=torch.float32)
+                part = conv2d_thin_scratch(G, B, Ho, Wo, co, k, ci, xs.device)
+                m.conv2d_thin_wgrad(xs.data_ptr(), dy.data_ptr(), dw.data_ptr(), co * ci * k * k,
+                                    db.data_ptr() if want_b else 0, co, part.data_ptr(), part.numel(), 0, G, B, H, W,
+                                    ci, ci, co, k, pad, _stream())
+            return dx, dw, db, None, None
         if ctx.new and conv2d_wg_ok(k, Wo, G, ci, co):
             if ctx.needs_input_grad[1] or want_b:
                 # dB comes from the dY tiles that the dW blocks stage: the kernel cannot skip dW, so a bias-only
