@@ -247,6 +247,8 @@ void conv2d_pack_w(uintptr_t w, int64_t ldw, uintptr_t img, uintptr_t imgt, int 
                    uintptr_t stream);
 void conv2d_fd(uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, int G, int B, int H, int W, int cin, int cs,
                int cout, int k, int pad, int dgrad, uintptr_t stream);
+void conv2d_ws(uintptr_t x, uintptr_t w, int64_t ldw, uintptr_t bias, int64_t ldb, uintptr_t y, int G, int B, int H,
+               int W, int cin, int cs, int cout, int k, int pad, int dgrad, uintptr_t stream);
 void conv2d_thin_fwd(uintptr_t x, uintptr_t w, int64_t ldw, uintptr_t bias, int64_t ldb, uintptr_t y, int G, int B,
                      int H, int W, int cin, int cs, int cout, int k, int pad, uintptr_t stream);
 int conv2d_thin_splits(int G, int B, int Ho, int Wo, int cout, int splits);
@@ -440,6 +442,7 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(conv2d_wg);
   DEF(conv2d_pack_w);
   DEF(conv2d_fd);
+  DEF(conv2d_ws);
   DEF(conv2d_thin_fwd);
   DEF(conv2d_thin_splits);
   DEF(conv2d_thin_wgrad);

@@ -1,5 +1,5 @@
 """Client-grouped layers for the batched 2-D image engine on the hand-written kernels (``conv2d_fd.hip``,
-``conv2d_thin.hip``, ``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``, ``gn_pool.hip``).
+``conv2d_ws.hip``, ``conv2d_thin.hip``, ``conv2d_any.hip``, ``conv2d_wg.hip``, ``linear_g.hip``, ``gn_pool.hip``).
 
 The small models of the reference's entry points (``lenet5``, ``cnn_cifar10/100``, the EMNIST CNNs, ``vgg11/16`` —
 ``fedml_experiments/standalone/subavg/main_subavg.py:143-158``) run G clients of a lockstep step as one pass over
@@ -13,7 +13,11 @@ group-stacked tensors ``[G*B, C, H, W]``: a deep copy of the model whose ``Conv2
   everywhere with ``NIDT_B2D_FD=0``; the thin first layers (at most 4 input channels, ``conv2d_thin_ok``) run their
   forward and their weight / bias gradient on ``conv2d_thin.hip`` (a dense contraction over k k Cin, the fp32
   weights read in place with no image packed, the gradient split over positions and summed in a fixed order;
-  ``NIDT_B2D_THIN=0`` routes them as every other layer); weight and bias gradient of the other layers on the MFMA
+  ``NIDT_B2D_THIN=0`` routes them as every other layer); the weight-bound deep 3 x 3 layers on small maps
+  (``conv2d_ws_ok``: vgg's layers from 128 input channels up, 16 x 16 maps and smaller) run forward and data
+  gradient on ``conv2d_ws.hip``, which reads the clients' fp32 blocks in place, so that such a layer packs no image at
+  all, in training and in evaluation (``NIDT_B2D_WS=0`` keeps the image paths, 2 routes every served layer);
+  weight and bias gradient of the other layers on the MFMA
   kernel of ``conv2d_wg.hip``, which owns each output element and writes fp32 in the parameter layout, the bf16 weight images
   from one ``conv2d_pack_w`` launch; ``NIDT_B2D_WGRAD=0`` keeps the staged fp32 weight-gradient kernel of
   ``conv2d_any.hip`` with its framework partial sum, bias sum and packing; the activations stay channels-last
@@ -145,6 +149,75 @@ def conv2d_fd_ok(k, pad, W, cin, cout, dgrad):
     return conv2d_fd_served(k, pad, W, cin, cout, dgrad) and (cout if dgrad else cin) >= FD_MIN_C
 
 
+def _ws_mode():
+    """``NIDT_B2D_WS``: 0 = no layer on ``conv2d_ws``, 1 = the layers ``conv2d_ws_ok`` accepts, 2 = every layer the
+    launcher serves (tests and measurements).  The default is 1: the vgg11 train step took 0.73 and its evaluation
+    0.40 of the time with 0 at 100 clients x 16 images, 0.96 and 0.77 at 8 x 64, against a [min .. max] spread of the
+    path with 0 below 1 percent (``profiles/r16_conv2d_ws.txt``)."""
+    return int(os.environ.get("NIDT_B2D_WS", "1"))
+
+
+WS_MAX_ROWS = 768
+WS_MIN_CIN = 128
+
+
+def conv2d_ws_tile(k, pad, B, H, W, dgrad):
+    """(positions per block, slab rows, dynamic LDS bytes) of a ``conv2d_ws`` launch, or None where the slab of whole
+    padded samples does not fit: the launcher's own arithmetic.  A tile of ``tm`` positions touches at most ``ns``
+    samples of P = Ho Wo positions of the map written (tm / P if P divides tm, 1 if tm divides P,
+    floor((tm + 2 P - 2) / P) otherwise, B at most), each a slab of (Ho + k - 1)(Wo + k - 1) rows of 48 bytes, next to
+    k k weight tiles of 3088 bytes; at most ``WS_MAX_ROWS`` rows and 64 KiB; 256 positions from B P = 256 up where
+    they fit, else 64."""
+    Ho, Wo = (H, W) if dgrad else (H + 2 * pad - k + 1, W + 2 * pad - k + 1)
+    if Ho <= 0 or Wo <= 0:
+        return None
+    P = Ho * Wo
+
+    def tile(tm):
+        ns = tm // P if tm % P == 0 else 1 if P % tm == 0 else (tm + 2 * P - 2) // P
+        rows = min(ns, B) * (Ho + k - 1) * (Wo + k - 1)
+        lds = 2 * (k * k * (64 * 24 + 8) + rows * 24)
+        return (tm, rows, lds) if rows <= WS_MAX_ROWS and lds <= 65536 else None
+
+    small = tile(64)
+    return small and ((B * P >= 256 and tile(256)) or small)
+
+
+def conv2d_ws_served(k, pad, B, H, W, cin, cout, dgrad):
+    """The launcher's rule of ``conv2d_ws`` for a layer described by its forward (``B`` images of ``H`` x ``W`` per
+    client): kernels up to 3 x 3, the contraction channel count (cin forward, cout data gradient; its stride is the
+    same number here) a multiple of 8, padding within the kernel for the data gradient, and the whole padded samples
+    of a tile within the LDS budget (``conv2d_ws_tile``): small maps."""
+    return (1 <= k <= 3 and (cout if dgrad else cin) % 8 == 0 and pad >= 0 and (pad <= k - 1 or not dgrad)
+            and conv2d_ws_tile(k, pad, B, H, W, dgrad) is not None)
+
+
+def conv2d_ws_ok(k, pad, B, H, W, cin, cout, dgrad):
+    """The layers whose forward / data gradient runs on ``conv2d_ws``; everything else keeps its image and ``conv2d_fd`` /
+    ``conv2d_any_fwd``.
+
+    * the launcher's rule (``conv2d_ws_served``) for this direction AND for the forward: the data gradient goes to
+      ``conv2d_ws`` only together with the forward, so that the layer packs nothing.  With the forward on ``conv2d_ws``
+      the ``conv2d_pack_w`` launch serves ``conv2d_fd``'s data gradient alone and belongs to its cost;
+    * the measured rule (``profiles/r16_conv2d_ws.txt``, the 3 x 3, pad 1 layers of vgg11 / vgg16 on 16 x 16 .. 2 x 2
+      maps, 100 clients x 16 images / 8 x 64, the parent path interleaved in the same run): k = 3 and at least
+      ``WS_MIN_CIN`` = 128 input channels.  Forward against ``conv2d_pack_w`` + ``conv2d_fd``: 1.28x - 4.39x / 1.23x -
+      1.70x on the six layers from 128 channels up, each beyond the parent's [min .. max]; 64 -> 128 on 16 x 16 maps
+      ran 1.13x / 1.14x with a difference equal to the parent's spread (0.019 / 0.006 ms), not beyond it: it stays.
+      ``HipConv2dFn`` forward + backward, nothing packed against the parent routing: 1.11x - 1.92x at 100 x 16, all
+      six beyond the spread; at 8 x 64 three are beyond it (128 -> 128, 256 -> 256, 512 -> 512 on 4 x 4: 1.06x -
+      1.19x) and three are inside it (1.00x - 1.05x), none slower.  Kernel against kernel the data gradient alone
+      is NOT always faster (0.52x on 2 x 2 maps at 100 x 16, 0.65x - 0.92x on 4 of 7 layers at 8 x 64: it re-reads
+      fp32 where ``conv2d_fd`` reads a bf16 image that the forward paid for); what it saves is the pack (0.71 ms
+      against 0.11 ms of lost kernel time on that 2 x 2 layer).  The column "``conv2d_fd`` data gradient + pack" was
+      not timed as one call: it is the sum of two columns; the ``HipConv2dFn`` column is the direct measurement.
+      Not measured: k = 1 and 2, paddings other than 1, non-square maps, channel counts off the vgg tables, and a
+      layer with the forward on ``conv2d_ws`` and the data gradient on ``conv2d_fd``; k = 1, 2 stay on the parent
+      path, the others follow the rule above."""
+    return (conv2d_ws_served(k, pad, B, H, W, cin, cout, dgrad) and conv2d_ws_served(k, pad, B, H, W, cin, cout, False)
+            and k == 3 and cin >= WS_MIN_CIN)
+
+
 def _hip_thin_on():
     return os.environ.get("NIDT_B2D_THIN", "1") != "0"
 
@@ -213,7 +286,10 @@ class HipConv2dFn(torch.autograd.Function):
     reads the saved forward image and no transposed image is packed; 0 keeps ``conv2d_any_fwd`` for both.  With
     ``NIDT_B2D_THIN=1`` (the default) a layer that ``conv2d_thin_ok`` accepts runs its forward on ``conv2d_thin_fwd``
     (whatever the other two switches say: no image is packed) and, with ``NIDT_B2D_WGRAD=1``, its weight / bias
-    gradient on ``conv2d_thin_wgrad``; its data gradient (tests only) stays on ``conv2d_any_fwd``."""
+    gradient on ``conv2d_thin_wgrad``; its data gradient (tests only) stays on ``conv2d_any_fwd``.  With
+    ``NIDT_B2D_WS=1`` (the default) each direction that ``conv2d_ws_ok`` accepts (2: that ``conv2d_ws_served`` accepts)
+    runs on ``conv2d_ws`` on the fp32 blocks in place; ``conv2d_pack_w`` is launched only if some direction of the
+    layer still reads an image."""
 
     @staticmethod
     def forward(ctx, x, w, b, G, pad):
@@ -233,18 +309,31 @@ class HipConv2dFn(torch.autograd.Function):
             bb, ldb = _client_blocks(b.detach()) if b is not None else (None, 0)
             m.conv2d_thin_fwd(xs.data_ptr(), wb.data_ptr(), ldw, bb.data_ptr() if b is not None else 0, ldb,
                               y.data_ptr(), G, B, H, W, ci, ci, co, k, pad, _stream())
-            ctx.fd_d = False  # a data gradient (tests only) packs its transposed image in the backward
+            ctx.fd_d = ctx.ws_d = False  # a data gradient (tests only) packs its transposed image in the backward
             ctx.save_for_backward(xs, w, None)
             return y.permute(0, 3, 1, 2)
-        fd = _hip_fd_on()
-        ctx.fd_d = fd and ctx.needs_input_grad[0] and conv2d_fd_ok(k, pad, W, ci, co, True)
-        wt = None
-        if ctx.new:
-            wp, wt = pack_conv_images(w.detach(), ctx.needs_input_grad[0] and not ctx.fd_d)
-        else:
+        fd, ws = _hip_fd_on(), _ws_mode()
+        ws_rule = conv2d_ws_served if ws == 2 else conv2d_ws_ok
+        ws_f = ws > 0 and ws_rule(k, pad, B, H, W, ci, co, False)
+        ctx.ws_d = ws > 0 and ctx.needs_input_grad[0] and ws_rule(k, pad, B, H, W, ci, co, True)
+        ctx.fd_d = fd and ctx.needs_input_grad[0] and not ctx.ws_d and conv2d_fd_ok(k, pad, W, ci, co, True)
+        # the forward image: read by every forward kernel but conv2d_ws and by conv2d_fd's data gradient; the
+        # transposed image: conv2d_any_fwd's data gradient.  A layer with both directions on conv2d_ws packs nothing
+        need_img = not ws_f or ctx.fd_d
+        need_t = ctx.needs_input_grad[0] and not (ctx.fd_d or ctx.ws_d)
+        wp = wt = None
+        if ctx.new and (need_img or need_t):
+            wp, wt = pack_conv_images(w.detach(), need_t)
+        elif need_img:
             wp = pack_conv_w(w.detach())
-        bias = b.detach().float().contiguous() if b is not None else None
-        if fd and conv2d_fd_ok(k, pad, W, ci, co, False):
+        bias = b.detach().float().contiguous() if b is not None and not ws_f else None
+        if ws_f:  # the fp32 weights and bias read where they lie
+            xs = _aligned16(xs)
+            wb, ldw = _client_blocks(w.detach())
+            bb, ldb = _client_blocks(b.detach()) if b is not None else (None, 0)
+            m.conv2d_ws(xs.data_ptr(), wb.data_ptr(), ldw, bb.data_ptr() if b is not None else 0, ldb, y.data_ptr(),
+                        G, B, H, W, ci, ci, co, k, pad, 0, _stream())
+        elif fd and conv2d_fd_ok(k, pad, W, ci, co, False):
             xs = _aligned16(xs)
             m.conv2d_fd(xs.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else 0, y.data_ptr(), G, B,
                         H, W, ci, ci, co, k, pad, 0, _stream())
@@ -267,7 +356,12 @@ class HipConv2dFn(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dxs = torch.empty(N, H, W, ci, device=xs.device, dtype=torch.bfloat16)
-            if ctx.fd_d:
+            if ctx.ws_d:
+                dy = _aligned16(dy)
+                wb, ldw = _client_blocks(w.detach())
+                m.conv2d_ws(dy.data_ptr(), wb.data_ptr(), ldw, 0, 0, dxs.data_ptr(), G, B, H, W, ci, co, co, k, pad, 1,
+                            _stream())
+            elif ctx.fd_d:
                 dy = _aligned16(dy)
                 m.conv2d_fd(dy.data_ptr(), wt.data_ptr(), 0, dxs.data_ptr(), G, B, H, W, ci, co, co, k, pad, 1,
                             _stream())
