@@ -31,6 +31,11 @@ int64_t rows_pair_sqdist_workspace(int64_t K, int64_t n);
 void rows_pair_sqdist(uintptr_t rows, int64_t stride, uintptr_t ridx, int64_t K, int64_t n, uintptr_t part,
                       uintptr_t D, int64_t accumulate, uintptr_t stream);
 void krum_select(uintptr_t D, int64_t K, int64_t f, int64_t multi, uintptr_t sel, uintptr_t score, uintptr_t stream);
+int64_t rows_geomed_workspace(int64_t K, int64_t n);
+void rows_geomed_step(uintptr_t rows, int64_t stride, uintptr_t ridx, int64_t K, int64_t n, uintptr_t beta,
+                      uintptr_t z_out, uintptr_t part, uintptr_t stream);
+void geomed_weights(uintptr_t part, int64_t nblocks, int64_t K, uintptr_t dsq, int64_t accumulate, uintptr_t alpha,
+                    double nu, uintptr_t beta_out, uintptr_t obj, uintptr_t stream);
 // secagg.hip
 int64_t secagg_blocks(int64_t P);
 void secagg_upload(uintptr_t rows, int64_t stride, uintptr_t ridx, uintptr_t cids, uintptr_t wts, uintptr_t poff,
@@ -326,6 +331,9 @@ PYBIND11_MODULE(_nidt_hip, m) {
   DEF(rows_pair_sqdist_workspace);
   DEF(rows_pair_sqdist);
   DEF(krum_select);
+  DEF(rows_geomed_workspace);
+  DEF(rows_geomed_step);
+  DEF(geomed_weights);
   DEF(secagg_blocks);
   DEF(secagg_upload);
   DEF(secagg_masked_sum);

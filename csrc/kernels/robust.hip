@@ -4,8 +4,10 @@
 //   rows_order_mean  : out[j] = mean of the order statistics lo .. hi-1 of column j over the K listed rows
 //   rows_pair_sqdist : D[i][k] (+)= sum_j ((double)(a_i[j] - a_k[j]))^2   (fp32 difference, exact fp64 square, fp64 sums)
 //   krum_select      : score[i] = sum of the m smallest D[i][k], k != i; sel = the `multi` smallest scores
+//   rows_geomed_step : z[j] = sum_i fl(beta_i a_i[j]) and part[block][i] = sum_j ((double)(a_i[j] - z[j]))^2 in one
+//                      read of the rows; geomed_weights turns the distances into the next Weiszfeld weights
 //
-// All three read an fp32 row matrix through a base pointer, a row stride (16-B aligned rows, stride % 4 == 0) and an
+// The row kernels read an fp32 row matrix through a base pointer, a row stride (16-B aligned rows, stride % 4 == 0) and an
 // int32 device list ridx[K] of row numbers: the list gives the client order, the rows need not be contiguous, rows
 // that are not listed and columns >= n are never read.  No atomics; every result is a function of the listed rows'
 // contents, K and n only.
@@ -370,6 +372,233 @@ void krum_select(uintptr_t D, int64_t K, int64_t f, int64_t multi, uintptr_t sel
                      ptr<double>(score));
   hipLaunchKernelGGL(k_krum_pick, dim3(1), dim3(kRobThreads), 0, st, ptr<const double>(score), (int)K, (int)multi,
                      ptr<int>(sel));
+  NIDT_CHECK(hipGetLastError());
+}
+
+// ---- geometric median (RFA): one fused Weiszfeld pass ----
+// A tile is TC = 2^lt columns of all K rows, TC = 16384 / max(16, K rounded up to a power of two): 1024 columns up to
+// K = 16 down to 64 at K = 256, so a tile's fp32 copy fits 64 KiB of LDS and a thread never owns more than kGeoRows
+// rows.  Thread (g, q) of the 512 owns the 16-byte column quad q of the rows g, g + G, g + 2 G, ... (G = 2048 / TC row
+// groups; q is the fast index: a wave reads pieces of up to 1 KiB of rows).  Two blocks fit a CU.  Per tile:
+//   1. the quads, loaded from HBM once into registers, are stashed in LDS as [row][column];
+//   2. the next tile's loads are issued into the same registers; one thread per column adds fl(beta_i * x_i) over the
+//      stash in client order (rows with beta_i == 0 are skipped: their NaN or Inf cannot leak in) and writes z to LDS
+//      and to z_out;
+//   3. every thread takes (double)(x - z)^2 of its own quads, read back from the stash, against the z quad into one
+//      fp64 sum per owned row.
+// Columns >= n are loaded as 0 and get z = 0 (difference 0), never read or written.  A block walks `tpb` consecutive
+// tiles (at most kGeoMaxBlocks blocks per launch) and reduces its row sums once at the end: xor shuffles over the
+// lanes that share a row group, then over the waves that do through LDS, both in a fixed order.  One fp64 partial
+// per (block, row), no atomics.
+constexpr int kGeoThreads = 512;
+constexpr int kGeoRows = 8;
+constexpr int kGeoMaxBlocks = 1024;
+
+static int geomed_log2_tile(int64_t K) {
+  int lk = 4;
+  while ((int64_t(1) << lk) < K) ++lk;
+  return 14 - lk;
+}
+
+// (tiles per block, blocks) of n columns: a function of (K, n) only
+static int64_t geomed_grid(int64_t K, int64_t n, int64_t* tpb) {
+  const int64_t ntiles = (n + (int64_t(1) << geomed_log2_tile(K)) - 1) >> geomed_log2_tile(K);
+  *tpb = ntiles > kGeoMaxBlocks ? (ntiles + kGeoMaxBlocks - 1) / kGeoMaxBlocks : 1;
+  return (ntiles + *tpb - 1) / *tpb;
+}
+
+int64_t rows_geomed_workspace(int64_t K, int64_t n) {
+  int64_t tpb;
+  return geomed_grid(K, n, &tpb) * K;
+}
+
+__global__ __launch_bounds__(kGeoThreads, 4) void k_rows_geomed_step(const float* __restrict__ rows, int64_t stride,
+                                                                  const int* __restrict__ ridx, int K, int64_t n,
+                                                                  const float* __restrict__ beta, int lt, int tpb,
+                                                                  float* __restrict__ z_out,
+                                                                  double* __restrict__ part) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) unsigned char rob_smem[];
+  __shared__ int s_ridx[kRobMaxK];
+  __shared__ float s_beta[kRobMaxK];
+  __shared__ double s_red[kRobMaxK];
+  const int TC = 1 << lt;
+  float* s_x = reinterpret_cast<float*>(rob_smem);  // [K][TC]
+  float* s_z = s_x + (size_t)K * TC;                // [TC]
+  const int lq = lt - 2;                            // log2 of the quads per row piece
+  const int q = threadIdx.x & ((1 << lq) - 1), g = threadIdx.x >> lq, lG = 9 - lq;
+  for (int k = threadIdx.x; k < K; k += kGeoThreads) {
+    s_ridx[k] = ridx[k];
+    s_beta[k] = beta[k];
+  }
+  __syncthreads();
+  const int64_t t0 = (int64_t)blockIdx.x * tpb;
+  const int64_t ntiles = (n + TC - 1) >> lt;
+  const int64_t t1 = t0 + tpb < ntiles ? t0 + tpb : ntiles;
+  float4 v[kGeoRows];
+  auto load = [&](int64_t tile) {
+    const int64_t col = (tile << lt) + 4 * q;
+#pragma unroll
+    for (int r = 0; r < kGeoRows; ++r) {
+      const int i = g + (r << lG);
+      v[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (i < K) {
+        const float* p = rows + (int64_t)s_ridx[i] * stride;
+        if (col + 3 < n) {
+          v[r] = *reinterpret_cast<const float4*>(p + col);
+        } else {
+          if (col < n) v[r].x = p[col];
+          if (col + 1 < n) v[r].y = p[col + 1];
+          if (col + 2 < n) v[r].z = p[col + 2];
+        }
+      }
+    }
+  };
+  double acc[kGeoRows];
+#pragma unroll
+  for (int r = 0; r < kGeoRows; ++r) acc[r] = 0.0;
+  if (t0 < t1) load(t0);
+  for (int64_t tile = t0; tile < t1; ++tile) {
+#pragma unroll
+    for (int r = 0; r < kGeoRows; ++r) {
+      const int i = g + (r << lG);
+      if (i < K) *reinterpret_cast<float4*>(s_x + i * TC + 4 * q) = v[r];
+    }
+    __syncthreads();  // the stash is whole
+    if (tile + 1 < t1) load(tile + 1);  // in flight while this tile is summed
+    for (int c = threadIdx.x; c < TC; c += kGeoThreads) {
+      const int64_t col = (tile << lt) + c;
+      float z = 0.f;
+      if (col < n) {
+        for (int i = 0; i < K; ++i) {
+          const float b = s_beta[i];
+          if (b != 0.f) z = z + b * s_x[i * TC + c];  // rounds twice: contraction is off in this kernel
+        }
+        z_out[col] = z;
+      }
+      s_z[c] = z;
+    }
+    __syncthreads();  // z is whole
+    const float4 z4 = *reinterpret_cast<const float4*>(s_z + 4 * q);
+#pragma unroll
+    for (int r = 0; r < kGeoRows; ++r) {
+      const int i = g + (r << lG);
+      if (i < K) {
+        const float4 x = *reinterpret_cast<const float4*>(s_x + i * TC + 4 * q);
+        const double dx = (double)(x.x - z4.x), dy = (double)(x.y - z4.y), dz = (double)(x.z - z4.z),
+                     dw = (double)(x.w - z4.w);
+        acc[r] = fma(dx, dx, acc[r]);  // the square of an fp32 value is exact in fp64: one rounding, as acc + d * d
+        acc[r] = fma(dy, dy, acc[r]);
+        acc[r] = fma(dz, dz, acc[r]);
+        acc[r] = fma(dw, dw, acc[r]);
+      }
+    }
+    __syncthreads();  // the stash and z may be overwritten
+  }
+  const int span = lq < 6 ? 1 << lq : 64;  // lanes of a wave that share a row group
+#pragma unroll
+  for (int r = 0; r < kGeoRows; ++r)
+    for (int o = span >> 1; o > 0; o >>= 1) acc[r] += __shfl_xor(acc[r], o, 64);
+  const int nwq = lq > 6 ? 1 << (lq - 6) : 1;  // waves that share a row group (K <= 32 when 2, K <= 16 when 4)
+  for (int wq = 0; wq < nwq; ++wq) {
+    __syncthreads();
+    if ((q & 63) == 0 && (q >> 6) == wq) {
+#pragma unroll
+      for (int r = 0; r < kGeoRows; ++r) {
+        const int i = g + (r << lG);
+        if (i < K) s_red[i] = wq ? s_red[i] + acc[r] : acc[r];
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < K; i += kGeoThreads) part[(int64_t)blockIdx.x * K + i] = s_red[i];
+}
+
+void rows_geomed_step(uintptr_t rows, int64_t stride, uintptr_t ridx, int64_t K, int64_t n, uintptr_t beta,
+                      uintptr_t z_out, uintptr_t part, uintptr_t stream) {
+  NIDT_REQUIRE(stride % 4 == 0 && stride >= n && (rows & 15) == 0 && (ridx & 3) == 0 && (beta & 3) == 0 &&
+                   (z_out & 3) == 0 && (part & 7) == 0,
+               "rows_geomed_step: 16-byte aligned rows (stride % 4 == 0, stride >= n)");
+  NIDT_REQUIRE(K >= 1 && K <= kRobMaxK && n >= 0 && rows != 0 && ridx != 0 && beta != 0 && z_out != 0 && part != 0,
+               "rows_geomed_step: arguments (1 <= K <= 256)");
+  if (n == 0) return;
+  const int lt = geomed_log2_tile(K);
+  int64_t tpb;
+  const int64_t nblocks = geomed_grid(K, n, &tpb);
+  NIDT_REQUIRE(tpb < (int64_t(1) << 31), "rows_geomed_step: n");
+  const int lds = (int)((K + 1) << lt) * 4;
+  NIDT_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_geomed_step),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  hipLaunchKernelGGL(k_rows_geomed_step, dim3((unsigned)nblocks), dim3(kGeoThreads), lds, as_stream(stream),
+                     ptr<const float>(rows), stride, ptr<const int>(ridx), (int)K, n, ptr<const float>(beta), lt,
+                     (int)tpb, ptr<float>(z_out), ptr<double>(part));
+  NIDT_CHECK(hipGetLastError());
+}
+
+// Block i: the partials of row i are staged in LDS with parallel loads and added by one thread in ascending block
+// order (a thread reading them straight from global memory is a chain of load latencies); dsq[i] (+)= that sum.
+__global__ __launch_bounds__(kRobThreads) void k_geomed_dsq(const double* __restrict__ part, int nblocks, int K,
+                                                            double* __restrict__ dsq, int accumulate) {
+  __shared__ double sp[kGeoMaxBlocks];
+  const int i = blockIdx.x;
+  for (int b = threadIdx.x; b < nblocks; b += kRobThreads) sp[b] = part[(int64_t)b * K + i];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int b = 0; b < nblocks; ++b) t += sp[b];
+    dsq[i] = accumulate ? dsq[i] + t : t;
+  }
+}
+
+// One block, thread i = row i: d_i = sqrt(dsq_i), w_i = alpha_i / max(nu, d_i), or 0 where d_i is not finite or
+// alpha_i is 0; thread 0 adds the weights and the alpha_i d_i of the finite rows in client order.  All fp64.
+__global__ __launch_bounds__(kRobThreads) void k_geomed_beta(const double* __restrict__ dsq,
+                                                             const double* __restrict__ alpha, double nu, int K,
+                                                             float* __restrict__ beta_out, double* __restrict__ obj) {
+  __shared__ double s_w[kRobMaxK], s_o[kRobMaxK];
+  __shared__ int s_fin[kRobMaxK];
+  __shared__ double s_tot;
+  const int i = threadIdx.x;
+  double w = 0.0;
+  if (i < K) {
+    const double d = sqrt(dsq[i]), a = alpha[i];
+    const bool fin = isfinite(d);
+    w = (fin && a != 0.0) ? a / (d > nu ? d : nu) : 0.0;
+    s_w[i] = w;
+    s_o[i] = fin ? a * d : 0.0;
+    s_fin[i] = (int)fin;
+  }
+  __syncthreads();
+  if (i == 0) {
+    double tw = 0.0, to = 0.0;
+    int nf = 0;
+    for (int k = 0; k < K; ++k) {
+      tw += s_w[k];
+      to += s_o[k];
+      nf += s_fin[k];
+    }
+    s_tot = tw;
+    *obj = nf ? to : __longlong_as_double(0x7ff8000000000000ll);
+  }
+  __syncthreads();
+  if (i < K) beta_out[i] = s_tot > 0.0 ? (float)(w / s_tot) : 0.f;
+}
+
+void geomed_weights(uintptr_t part, int64_t nblocks, int64_t K, uintptr_t dsq, int64_t accumulate, uintptr_t alpha,
+                    double nu, uintptr_t beta_out, uintptr_t obj, uintptr_t stream) {
+  NIDT_REQUIRE(K >= 1 && K <= kRobMaxK && nblocks >= 0 && nblocks <= kGeoMaxBlocks && dsq != 0 && (dsq & 7) == 0 &&
+                   (part & 7) == 0 && (part != 0 || nblocks == 0),
+               "geomed_weights: arguments (1 <= K <= 256, 0 <= nblocks <= 1024)");
+  NIDT_REQUIRE(beta_out == 0 || (alpha != 0 && obj != 0 && nu > 0 && (alpha & 7) == 0 && (obj & 7) == 0 &&
+                                 (beta_out & 3) == 0),
+               "geomed_weights: beta_out needs alpha, obj and nu > 0");
+  hipStream_t st = as_stream(stream);
+  if (nblocks > 0 || !accumulate)
+    hipLaunchKernelGGL(k_geomed_dsq, dim3((unsigned)K), dim3(kRobThreads), 0, st, ptr<const double>(part),
+                       (int)nblocks, (int)K, ptr<double>(dsq), (int)(accumulate != 0));
+  if (beta_out != 0)
+    hipLaunchKernelGGL(k_geomed_beta, dim3(1), dim3(kRobThreads), 0, st, ptr<const double>(dsq),
+                       ptr<const double>(alpha), nu, (int)K, ptr<float>(beta_out), ptr<double>(obj));
   NIDT_CHECK(hipGetLastError());
 }
 

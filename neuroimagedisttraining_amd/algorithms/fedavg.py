@@ -7,7 +7,7 @@ every client runs one extra local "fine-tune" pass from ``w_global`` and a final
 
 FedProx (new; BASELINE.json config 4) is FedAvg with the proximal term ``mu/2 ||w - w_g||^2``
 added to each local loss (``args.fedprox_mu``) and an optional robust aggregator
-(``args.aggregator`` in {``fedavg``, ``krum``, ``multikrum``, ``median``, ``trimmed_mean``}).
+(``args.aggregator`` in {``fedavg``, ``krum``, ``multikrum``, ``median``, ``trimmed_mean``, ``geomed``}).
 """
 from __future__ import annotations
 
@@ -68,7 +68,9 @@ class FedAvgAPI(APIBase):
         if kind == "fedavg":
             return super()._aggregate(w_locals)
         return R.robust_aggregate(kind, w_locals, f=int(getattr(self.args, "byzantine_f", 0) or 0),
-                                  trim_ratio=float(getattr(self.args, "trim_ratio", 0.1) or 0.1))
+                                  trim_ratio=float(getattr(self.args, "trim_ratio", 0.1) or 0.1),
+                                  iters=int(getattr(self.args, "geomed_iters", 4) or 4),
+                                  nu=float(getattr(self.args, "geomed_nu", 1e-6) or 1e-6))
 
     def _aggregate_secure(self, w_locals, round_idx=0, client_ids=None):
         out, self._secagg_keys = secure_aggregate(self.args, self.stat_info, w_locals, round_idx, client_ids,

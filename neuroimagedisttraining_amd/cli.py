@@ -12,8 +12,10 @@ the reference entry points.  Added flags:
 * ``--synthetic_abcd 1``, ``--n_per_client``: synthetic ABCD-shape cohort (no HDF5 needed); ``--synthetic_abcd 0
   --data_dir <cohort.nidtvol | dir>`` trains on the real cohort (site clients) on either path;
   ``--synthetic_size N``: N synthetic train images (N/5 test) for CIFAR/Tiny without data files.
-* FedProx / robust aggregation: ``--fedprox_mu``, ``--aggregator {fedavg,krum,multikrum,median,trimmed_mean}``,
-  ``--byzantine_f``, ``--trim_ratio``.
+* FedProx / robust aggregation: ``--fedprox_mu``, ``--aggregator {fedavg,krum,multikrum,median,trimmed_mean,geomed}``,
+  ``--byzantine_f``, ``--trim_ratio``.  ``geomed`` is the geometric median of the client models (RFA: ``--geomed_iters``
+  smoothed Weiszfeld passes from the mean, distances floored at ``--geomed_nu``; unweighted clients, clients whose
+  model is not finite are left out); on the HIP executor one fused kernel pass over the client rows per iteration.
 * ``--defense_type {none,norm_diff_clipping,weak_dp}``, ``--norm_bound``, ``--stddev`` (the names the reference's
   ``RobustAggregator`` reads): every client's update ``w_i - w_g`` over the weight parameters is clipped to an L2
   ball of radius ``norm_bound`` before the FedAvg mean; ``weak_dp`` then adds ``N(0, stddev^2)`` per client.  On the
@@ -134,9 +136,12 @@ def add_args(parser, algo):
     a("--heartbeat_s", type=float, default=0.0)  # >0: multi-rank failure detection (comm/failure.py)
     a("--augment", type=int, default=1)  # image datasets: the reference's train-time RandomCrop(pad 4) + flip
     a("--fedprox_mu", type=float, default=d.get("fedprox_mu", 0.0))
-    a("--aggregator", type=str, default="fedavg")
+    a("--aggregator", type=str, default="fedavg",
+      help="fedavg | krum | multikrum | median | trimmed_mean | geomed (geometric median, RFA) | secure")
     a("--byzantine_f", type=int, default=0)
     a("--trim_ratio", type=float, default=0.1)
+    a("--geomed_iters", type=int, default=4, help="--aggregator geomed: Weiszfeld passes (the first yields the mean)")
+    a("--geomed_nu", type=float, default=1e-6, help="--aggregator geomed: smoothing floor of the distances")
     a("--update_topk", type=float, default=0.0, help="send only the top-k fraction of each client's update")
     a("--defense_type", type=str, default="none", choices=list(DEFENSES),
       help="norm_diff_clipping: clip each client's update to --norm_bound; weak_dp: clip, then N(0, --stddev^2) noise")
@@ -404,6 +409,7 @@ def fl_config(args, algo):
                     snip_mask=g("snip_mask", True), frequency_of_the_test=args.frequency_of_the_test, seed=args.seed,
                     prox_mu=args.fedprox_mu if algo == "fedprox" else 0.0, group=args.group,
                     aggregator=args.aggregator, byzantine_f=args.byzantine_f, trim_ratio=args.trim_ratio,
+                    geomed_iters=g("geomed_iters", 4), geomed_nu=g("geomed_nu", 1e-6),
                     update_topk=args.update_topk, heartbeat_s=args.heartbeat_s,
                     rebalance=bool(g("rebalance", 0)),
                     stratified_sampling=bool(g("stratified_sampling", False)),

@@ -1,6 +1,6 @@
 """Robust aggregation (reference ``fedml_core/robustness/robust_aggregation.py:4-55``) plus the
 Byzantine-robust aggregators BASELINE.json asks for (Krum, Multi-Krum, coordinate-wise median,
-trimmed mean), which the reference lacks.
+trimmed mean) and the geometric median (RFA), which the reference lacks.
 
 Everything operates on flattened parameter vectors; states are flattened with
 :func:`vectorize_weight` (which, unlike the reference's ``torch.cat`` of unflattened tensors —
@@ -110,7 +110,24 @@ def trimmed_mean(M, trim_ratio=0.1):
     return S[b:K - b].mean(0)
 
 
-def robust_aggregate(kind, w_locals, f=0, trim_ratio=0.1):
+def geometric_median(M, iters=4, nu=1e-6):
+    """Geometric median of the rows of ``M`` by the smoothed Weiszfeld iteration (RFA, Pillutla et al.), unweighted
+    clients, in fp64, returned as fp32.  Rows whose norm is not finite are left out for good; the start is the mean
+    of the others; every pass weighs row i by ``1 / max(nu, |x_i - z|)``."""
+    X = M.double()
+    K = X.shape[0]
+    alpha = torch.isfinite((X * X).sum(1)).double() / K
+    X = torch.where(alpha[:, None] > 0, X, torch.zeros((), dtype=X.dtype, device=X.device))  # 0 * NaN stays out
+    beta = alpha / alpha.sum().clamp_min(1e-300)
+    for t in range(int(iters)):
+        z = beta @ X
+        if t + 1 < int(iters):
+            w = alpha / (X - z).norm(dim=1).clamp_min(nu)
+            beta = w / w.sum().clamp_min(1e-300)
+    return z.float()
+
+
+def robust_aggregate(kind, w_locals, f=0, trim_ratio=0.1, iters=4, nu=1e-6):
     """``w_locals`` = list of ``(n, state)``; returns the aggregated state."""
     states = [s for _, s in w_locals]
     M, shapes = stack_states(states)
@@ -122,6 +139,8 @@ def robust_aggregate(kind, w_locals, f=0, trim_ratio=0.1):
         v = coordinate_median(M)
     elif kind == "trimmed_mean":
         v = trimmed_mean(M, trim_ratio)
+    elif kind == "geomed":
+        v = geometric_median(M, iters, nu)
     elif kind == "fedavg":
         n = torch.tensor([float(k) for k, _ in w_locals], dtype=M.dtype, device=M.device)
         v = (n / n.sum()) @ M

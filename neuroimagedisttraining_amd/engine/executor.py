@@ -67,10 +67,13 @@ class FLConfig:
     prox_mu: float = 0.0          # FedProx proximal coefficient (0 = FedAvg/SalientGrads)
     group: int = 0                # max clients per lockstep launch (0 = all local clients)
     test_batch: int = 256
-    aggregator: str = "fedavg"    # fedavg | krum | multikrum | median | trimmed_mean (BASELINE config 4) | secure
+    aggregator: str = "fedavg"    # fedavg | krum | multikrum | median | trimmed_mean (BASELINE config 4) | geomed |
+                                  # secure
     byzantine_f: int = 0          # Krum's assumed number of Byzantine clients
     multikrum_m: int = 0          # Multi-Krum: number of selected clients (0 = K - f)
     trim_ratio: float = 0.1       # trimmed mean: fraction cut from each end per coordinate
+    geomed_iters: int = 4         # geometric median (RFA): Weiszfeld passes (the first one yields the mean)
+    geomed_nu: float = 1e-6       # geometric median: smoothing floor of the distances in the weights
     sparse_aggregate: bool = True  # SalientGrads: all-reduce only the coordinates kept by the global mask
     update_topk: float = 0.0      # >0: each client sends only its top-k |update| (values + int32 indices,
                                   # k = update_topk * P) through an RCCL all-gather (BASELINE config 5)
@@ -125,6 +128,8 @@ class FLConfig:
                 raise ValueError("aggregator=secure needs 1 <= secagg_scale <= 2^24, 0 <= secagg_dropout < 1 and "
                                  "secagg_threshold >= 0 (got %s, %s, %s)"
                                  % (self.secagg_scale, self.secagg_dropout, self.secagg_threshold))
+        if not (int(self.geomed_iters) >= 1 and self.geomed_nu > 0):
+            raise ValueError("geomed_iters >= 1 and geomed_nu > 0 (got %s, %s)" % (self.geomed_iters, self.geomed_nu))
         if self.defense_type not in ("none", "norm_diff_clipping", "weak_dp"):
             raise ValueError("defense_type %r: one of none | norm_diff_clipping | weak_dp" % (self.defense_type,))
         if self.defense_type != "none":

@@ -1,7 +1,11 @@
-"""Krum, Multi-Krum, coordinate median and trimmed mean over the client rows (``csrc/kernels/robust.hip``).
+"""Krum, Multi-Krum, coordinate median, trimmed mean and the geometric median (RFA) over the client rows
+(``csrc/kernels/robust.hip``).
 
-Three primitives read an fp32 row matrix in place through a list ``ridx`` of row numbers (the list is the client
-order; rows that are not listed and columns past ``n`` are never touched):
+:func:`geomed_step` is one smoothed Weiszfeld pass (Pillutla et al., RFA) in one read of the rows: the weighted row sum
+``z`` (a sequential fp32 sum in client order, rows of weight 0 skipped) and every row's squared distance to that ``z``
+(fp32 difference, fp64 sums); :func:`geomed_weights` makes the next weights ``alpha_i / max(nu, d_i)`` of them, 0 for a
+row whose distance is not finite.  Three more primitives read an fp32 row matrix in place through a list ``ridx`` of
+row numbers (the list is the client order; rows that are not listed and columns past ``n`` are never touched):
 
 * :func:`order_mean` — per column, the mean of the order statistics ``lo .. hi-1`` of the listed rows (median:
   ``lo = (K-1)//2, hi = K//2 + 1``; trimmed mean: ``lo = b, hi = K - b``): a sequential fp32 sum in ascending rank and
@@ -28,7 +32,7 @@ import torch
 from .. import ops
 from ..parallel import runtime as rt
 
-KINDS = ("krum", "multikrum", "median", "trimmed_mean")
+KINDS = ("krum", "multikrum", "median", "trimmed_mean", "geomed")
 MAX_K = 256
 
 
@@ -166,6 +170,94 @@ def krum_select(D, f, multi, hip=None):
     return torch.from_numpy(sel).to(torch.int32).to(D.device), torch.from_numpy(score).to(D.device)
 
 
+# ------------------------------------------------------------------------------------------------ geometric median
+def geomed_step_twin(M, beta):
+    """(z ``[n]`` fp32, dsq ``[K]`` fp64) from ``M`` ``[K, n]`` and the fp32 weights ``beta`` ``[K]``, in the kernel's
+    order: ``z`` = 0, then ``z + fl(beta_i * M_i)`` over the rows in client order, product and sum rounded separately,
+    rows of weight 0 skipped; ``dsq_i`` = the fp64 sum of the squared fp32 differences ``M_i - z``."""
+    M = M.float()
+    z = torch.zeros(M.shape[1], dtype=torch.float32, device=M.device)
+    for i, b in enumerate(beta.float().tolist()):
+        if b != 0.0:
+            z = z + torch.full((1,), b, dtype=torch.float32, device=M.device) * M[i]
+    d = (M - z).double()
+    return z, (d * d).sum(1)
+
+
+def geomed_weights_twin(dsq, alpha, nu):
+    """(beta ``[K]`` fp32, objective fp64) from the squared distances and the fp64 client weights ``alpha``: numpy, in
+    the kernel's order.  ``w_i = alpha_i / max(nu, d_i)``, 0 where ``d_i`` is not finite or ``alpha_i`` is 0;
+    ``beta = w / sum w`` (all 0 when no weight is left); the objective ``sum alpha_i d_i`` runs over the finite rows
+    and is NaN when there is none.  Sequential fp64 sums in client order."""
+    as_np = lambda t: np.asarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float64)  # noqa: E731
+    with np.errstate(invalid="ignore"):
+        d = np.sqrt(as_np(dsq))
+    a = as_np(alpha)
+    fin = np.isfinite(d)
+    w = np.zeros_like(d)
+    tw, to = np.float64(0.0), np.float64(0.0)
+    for i in range(d.shape[0]):
+        if fin[i]:
+            if a[i] != 0.0:
+                w[i] = a[i] / max(float(nu), d[i])
+            to = to + a[i] * d[i]
+        tw = tw + w[i]
+    beta = (w / tw).astype(np.float32) if tw > 0 else np.zeros(d.shape[0], dtype=np.float32)
+    return torch.from_numpy(beta), torch.tensor(float(to) if fin.any() else float("nan"), dtype=torch.float64)
+
+
+def geomed_step(mat, ridx, n, beta, z, dsq, accumulate=False, hip=None):
+    """One fused Weiszfeld pass over ``mat[ridx, :n]``: ``z[:n]`` = the ``beta``-weighted row sum (rows of weight 0
+    are skipped, so a NaN row of weight 0 cannot leak in) and ``dsq`` ``[K]`` fp64 (+)= every listed row's squared
+    distance to that ``z``.  The rows are read once.  Nothing past ``z[n]`` is written."""
+    ridx = _ridx(ridx, mat.device)
+    K = ridx.numel()
+    if not 1 <= K <= MAX_K:
+        raise ValueError("geomed_step: 1 <= K <= %d (K=%d)" % (MAX_K, K))
+    assert beta.dtype == torch.float32 and beta.is_contiguous() and beta.numel() == K and beta.device == mat.device
+    assert dsq.dtype == torch.float64 and dsq.is_contiguous() and dsq.numel() == K and dsq.device == mat.device
+    use = _use_hip(mat, hip)
+    if n == 0:
+        if not accumulate:
+            dsq.zero_()
+        return z
+    if use:
+        assert z.dtype == torch.float32 and z.is_contiguous() and z.numel() >= n and z.device == mat.device
+        m, st = ops.ext(), ops.stream()
+        nw = m.rows_geomed_workspace(K, n)
+        part = torch.empty(nw, dtype=torch.float64, device=mat.device)
+        m.rows_geomed_step(mat.data_ptr(), mat.stride(0), ridx.data_ptr(), K, n, beta.data_ptr(), z.data_ptr(),
+                           part.data_ptr(), st)
+        m.geomed_weights(part.data_ptr(), nw // K, K, dsq.data_ptr(), 1 if accumulate else 0, 0, 0.0, 0, 0, st)
+        return z
+    zt, dt = geomed_step_twin(mat.index_select(0, ridx.long())[:, :n], beta)
+    z[:n] = zt
+    if accumulate:
+        dsq += dt
+    else:
+        dsq.copy_(dt)
+    return z
+
+
+def geomed_weights(dsq, alpha, nu, hip=None):
+    """(beta ``[K]`` fp32, objective fp64 scalar) on ``dsq``'s device: the next pass's weights from the distances."""
+    K = dsq.numel()
+    if not (1 <= K <= MAX_K and nu > 0):
+        raise ValueError("geomed_weights: 1 <= K <= %d and nu > 0 (K=%d nu=%s)" % (MAX_K, K, nu))
+    use = dsq.device.type == "cuda" if hip is None else bool(hip)
+    if use:
+        if not (dsq.device.type == "cuda" and dsq.dtype == alpha.dtype == torch.float64 and dsq.is_contiguous()
+                and alpha.is_contiguous() and alpha.numel() == K and alpha.device == dsq.device):
+            raise ValueError("geomed_weights kernel needs contiguous fp64 CUDA vectors")
+        beta = torch.empty(K, dtype=torch.float32, device=dsq.device)
+        obj = torch.empty((), dtype=torch.float64, device=dsq.device)
+        ops.ext().geomed_weights(0, 0, K, dsq.data_ptr(), 1, alpha.data_ptr(), float(nu), beta.data_ptr(),
+                                 obj.data_ptr(), ops.stream())
+        return beta, obj
+    beta, obj = geomed_weights_twin(dsq, alpha, nu)
+    return beta.to(dsq.device), obj.to(dsq.device)
+
+
 # ------------------------------------------------------------------------------------------------ driver
 def column_chunks(K, ncols, budget=2e9):
     """[(first column, width)]: chunks of a ``K``-row section whose gathered copy stays under ``budget`` bytes.  A
@@ -187,7 +279,7 @@ def _runs(rows):
 
 
 def aggregate(kind, theta, bufs, P, Q, local_rows, local_clients, sampled, owner, info, out_w, out_b, f=0, multi=1,
-              trim_ratio=0.1, budget=2e9, hip=None):
+              trim_ratio=0.1, budget=2e9, hip=None, iters=4, nu=1e-6):
     """Robust aggregate of the sampled clients' (params, buffers) into ``out_w`` ``[P]`` / ``out_b`` ``[Q]``.
 
     ``theta`` / ``bufs``: this rank's row matrices; ``local_rows`` / ``local_clients``: the rows of the sampled
@@ -199,7 +291,15 @@ def aggregate(kind, theta, bufs, P, Q, local_rows, local_clients, sampled, owner
     the same kernel with ``ridx`` = the client-id permutation of the gathered rows.  Median / trimmed mean write each
     result chunk; Krum accumulates ``D`` over the parameter and buffer chunks in chunk order, selects, and forms the
     mean of the selected rows as a weighted row sum of the local rows (weight ``1 / multi``, in row order) plus one
-    all-reduce: plain Krum is an exact copy of the selected row.  Returns ``{"sel": selected client ids or None}``."""
+    all-reduce: plain Krum is an exact copy of the selected row.  Returns ``{"sel": selected client ids or None}``.
+
+    ``geomed`` (unweighted clients, params and buffers as one vector) runs :func:`geomed_step` over the chunks
+    ``iters + 1`` times: a screening pass with all weights 0 (``z`` = 0, the distances are the rows' norms; a row
+    whose norm is not finite gets ``alpha`` = 0 for good, the others ``1 / K``), then ``iters`` Weiszfeld passes,
+    pass 0 with ``alpha`` normalised (the mean of the finite rows), pass t with the weights :func:`geomed_weights`
+    made of pass t - 1's distances.  The last pass's ``z`` stays in ``out_w`` / ``out_b``; its distances only feed
+    ``"objective"`` (``sum alpha_i |x_i - z|``, an fp64 scalar on the device) of the returned dict.  No host
+    read-back.  Several ranks gather every chunk again in every pass: ``iters + 1`` times the median's traffic."""
     if kind not in KINDS:
         raise ValueError("unknown aggregator %r" % (kind,))
     order = sorted(int(c) for c in sampled)
@@ -231,6 +331,26 @@ def aggregate(kind, theta, bufs, P, Q, local_rows, local_clients, sampled, owner
                             else src[:, c0:c0 + w].index_select(0, rows_t))
         return rt.all_gather_sized(piece.view(-1), [n * w4 for n in cnt], info).view(K, w4)
 
+    if kind == "geomed":
+        if not (int(iters) >= 1 and nu > 0):
+            raise ValueError("geomed: iters >= 1 and nu > 0 (got %s, %s)" % (iters, nu))
+        jobs = [(src, out, c0, w) for src, ncols, out in ((theta, P, out_w), (bufs, Q, out_b))
+                for c0, w in column_chunks(K, ncols, budget)]
+        dsq = torch.zeros(K, dtype=torch.float64, device=dev)
+
+        def one_pass(beta):  # z of every chunk into out_w / out_b; dsq over both sections in chunk order
+            for j, (src, out, c0, w) in enumerate(jobs):
+                geomed_step(chunk_of(src, c0, w), ridx, w, beta, out[c0:c0 + w], dsq, accumulate=j > 0, hip=hip)
+
+        one_pass(torch.zeros(K, dtype=torch.float32, device=dev))  # screening: z = 0, dsq = the rows' squared norms
+        finite = torch.isfinite(dsq)
+        alpha = finite.double() / K
+        # alpha normalised: 1 / (number of finite rows), from an integer count, so the same bits on every device
+        beta = torch.where(finite, 1.0 / finite.sum().double().clamp_min(1.0), 0.0).float()
+        for _ in range(int(iters)):
+            one_pass(beta)
+            beta, obj = geomed_weights(dsq, alpha, nu, hip=None if hip is None else bool(hip) and dev.type == "cuda")
+        return {"sel": None, "objective": obj}
     krum = kind in ("krum", "multikrum")
     if krum:
         D = torch.zeros((K, K), dtype=torch.float64, device=dev)

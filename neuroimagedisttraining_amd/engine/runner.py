@@ -89,7 +89,7 @@ class StatInfo(dict):
     GPU loop never waits for a metric."""
 
     DEFERRED = ("global_test_acc", "global_test_loss", "person_test_acc", "person_test_loss", "test_acc",
-                "defense_clipped", "defense_max_ratio", "secagg_saturated", "secagg_dropped")
+                "defense_clipped", "defense_max_ratio", "secagg_saturated", "secagg_dropped", "geomed_objective")
 
     def __init__(self, flush, *a, **kw):
         super().__init__(*a, **kw)
@@ -1154,9 +1154,11 @@ class FLRunner:
         return res
 
     def aggregate_robust(self, sampled):
-        """Byzantine-robust aggregation (BASELINE config 4): Krum / Multi-Krum / coordinate median / trimmed mean
-        over the sampled clients, the same deterministic result on all ranks.  BN buffers follow the selected
-        clients for Krum and are coordinate-aggregated otherwise.
+        """Byzantine-robust aggregation (BASELINE config 4): Krum / Multi-Krum / coordinate median / trimmed mean /
+        geometric median over the sampled clients, the same deterministic result on all ranks.  BN buffers follow the
+        selected clients for Krum, are part of the vector for the geometric median (``cfg.geomed_iters`` Weiszfeld
+        passes; ``stat_info["geomed_objective"]``, the mean distance of the finite clients to the result, is read
+        with the deferred metrics) and are coordinate-aggregated otherwise.
 
         On the device the rows are aggregated where they lie by the kernels of ``robust.hip``
         (``engine/robust.py``: one process reads ``theta`` / ``bufs`` in place, several ranks gather one column
@@ -1172,9 +1174,13 @@ class FLRunner:
             res = RB.aggregate(kind, self.theta, self.bufs, self.P, self.Q, rows, loc, sampled, self.owner, self.info,
                                self.w_global, self.b_global, f=self.cfg.byzantine_f,
                                multi=self.cfg.multikrum_m or max(1, K - self.cfg.byzantine_f),
-                               trim_ratio=self.cfg.trim_ratio, hip=True)
+                               trim_ratio=self.cfg.trim_ratio, hip=True, iters=self.cfg.geomed_iters,
+                               nu=self.cfg.geomed_nu)
             if res["sel"] is not None:
                 self.stat_info["krum_selected"] = res["sel"]
+            if kind == "geomed":  # stays on the device; read where the deferred metrics are
+                self._defer_result(getattr(self, "_round_idx", 0), res["objective"].view(1),
+                                   recorder=self._record_geomed)
             self.stat_info["aggregate_elems"] = int(K * W)
             return
         from ..core import robustness as R
@@ -1193,11 +1199,19 @@ class FLRunner:
             agg = R.coordinate_median(M)
         elif kind == "trimmed_mean":
             agg = R.trimmed_mean(M, self.cfg.trim_ratio)
+        elif kind == "geomed":
+            agg = R.geometric_median(M, self.cfg.geomed_iters, self.cfg.geomed_nu)
+            d = (M.double() - agg.double()).norm(dim=1)
+            self.stat_info["geomed_objective"] = float(d[torch.isfinite(d)].sum() / M.shape[0])
         else:
             raise ValueError("unknown aggregator %r" % kind)
         self.w_global.copy_(agg[:self.P])
         self.b_global.copy_(agg[self.P:])
         self.stat_info["aggregate_elems"] = int(M.numel())
+
+    def _record_geomed(self, round_idx, r):
+        dict.__setitem__(self.stat_info, "geomed_objective", float(r[0]))
+        return dict(geomed_objective=float(r[0]))
 
     # ---------------------------------------------------------------------------------------------- evaluation
     def _split_of(self, c, which):
